@@ -5,8 +5,15 @@ reference's CPU semantics (Wolfe line search, lbfgs.hpp:38-100), N = 60000 synth
 samples (SURVEY.md §8(d) recipe), fp32, tolerance 0 (fixed iteration count). A "step" = one L-BFGS
 iteration (two-loop direction + line-search trials, each a fused loss+grad evaluation).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
+
+A plain run does what the headline figure needs: set-up, the untimed iterations, the K timed iterations,
+the result line (value, ms_per_step, the evaluation counts and the GFLOP/s they give). --full adds the
+per-section breakdown (kernel_ms_per_step), the dominant kernel's roofline and the CPU baseline to that
+line. Both modes time the same K iterations of the same trajectory. --dump-outputs DIR writes what the
+timed iterations computed (parameters, per-iteration record) as DIR/<name>.npy; inputs and seeds are fixed,
+so two builds can be compared output for output.
 
 With N > 1 the 60000 samples are split into contiguous shards (strong scaling; one RCCL all-reduce
 of [grad | loss] per evaluation, on the library's own communicator). The torch.distributed group is
@@ -47,6 +54,12 @@ def parse(argv=None):
     # few percent of the timed region instead of >10 % at 100
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-section breakdown pass "
+                         "(kernel_ms_per_step), the dominant kernel's roofline (HIP events inside the timed region, "
+                         "PMC traffic) and the CPU baseline (see --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--samples", type=int, default=60000)
     ap.add_argument("--dims", type=str, default="784,128,10")
     ap.add_argument("--acts", type=str, default="relu,linear")
@@ -57,7 +70,7 @@ def parse(argv=None):
     ap.add_argument("--init", choices=["cpu", "cuda"], default="cpu",
                     help="parameter-init stream: cpu = network.hpp:45-71 (all params N(0, s)), cuda = "
                          "network.cuh:36-59 (weights N(0, s), zero biases; the reference's GPU drivers)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--device-warmup", type=int, default=300,
                     help="L-BFGS: loss/gradient evaluations at the initial point before the run starts (untimed, the "
                          "same count on every rank; they leave the run's trajectory unchanged): the chip reaches its "
@@ -253,6 +266,31 @@ def isolate_stdout():
     os.dup2(2, 1)
 
 
+DUMP_BUDGET_BYTES = 64 << 20   # bound on everything one --dump-outputs run writes
+
+
+def dump_outputs(outdir, params, hist, it0):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as outdir/<name>.npy.
+    params.npy is the parameter vector the solver updated in place (float32); loss / grad_norm / alpha /
+    ls_trials / accepted are the record's rows of the timed steps (float64; the last row is the last
+    step's; the record's wall-clock column is not an output). An array over its share of the budget (1 MiB
+    per record column, the rest for the parameters) is written as a fixed, seeded sample of its elements
+    (index order kept)."""
+    os.makedirs(outdir, exist_ok=True)
+    n = hist.size
+    arrays = {k: np.asarray(getattr(hist, k)[it0:n], dtype=np.float64)
+              for k in ("loss", "grad_norm", "alpha", "ls_trials", "accepted")}
+    arrays["params"] = params.detach().cpu().numpy().astype(np.float32, copy=False).ravel()
+    left = DUMP_BUDGET_BYTES
+    for k, v in arrays.items():
+        share = (left if k == "params" else 1 << 20) - 4096      # the .npy header counts too
+        if v.nbytes > share:
+            keep = np.sort(np.random.default_rng(123).choice(v.size, share // v.itemsize, replace=False))
+            v = v[keep]
+        np.save(os.path.join(outdir, k + ".npy"), v)
+        left -= v.nbytes + 4096
+
+
 def main_slbfgs(a, pkg, ctx, world, rank):
     """BASELINE config 4: S-LBFGS epochs/s (+ grad-evals/s); every rank holds all N rows and evaluates its
     1/world slice of each minibatch, Hessian batch and full-gradient anchor (s_lbfgs.hpp:165-290)."""
@@ -267,32 +305,38 @@ def main_slbfgs(a, pkg, ctx, world, rank):
     kw = dict(M=10, L=10, b=a.slbfgs_b, b_H=a.slbfgs_bh, step=a.slbfgs_step, lam=1e-4, tol=0.0, dp_mode=a.slbfgs_dp)
     # one stateful solve for the breakdown, the warmup and the timed epochs
     run = pkg.SlbfgsRun(net, P, X, Y, **kw)
-    # first epoch with every kernel section timed: the breakdown and the dominant section
-    ctx.prof_select(None)
-    ctx.prof_sample(1)
-    ctx.prof_enable(True)
-    run.iterate(1)
-    breakdown = ctx.prof_read()
-    ctx.prof_enable(False)
     wep = 1
-    # the dominant GEMM section (the roofline is a GEMM's); at many ranks the epoch's all-reduce can take longer,
-    # but it runs once or twice per epoch, too rarely to sample
-    gemms = {k: v for k, v in breakdown.items() if k.split("[")[0] in ("gemm_fwd", "gemm_dw", "gemm_dx")}
-    dominant = max((gemms or breakdown).items(), key=lambda kv: kv[1][0])[0]
-    if world > 1:
-        obj = [dominant]
-        torch.distributed.broadcast_object_list(obj, src=0)
-        dominant = obj[0]
-    # timed region: only the dominant section carries events, on every PROF_EVERY-th launch (an event pair
-    # costs ~10 us of GPU time, and this section runs ~2x per inner step) while that still times
-    # PROF_MIN_LAUNCHES of them; the rows of every timed launch are counted (lbf_prof_read_work), so the
-    # sampled flops are exact whatever the batch sizes
-    every = max(1, min(PROF_EVERY, int(breakdown[dominant][1] * max(a.steps, 1) // PROF_MIN_LAUNCHES)))
-    ctx.prof_select(dominant)
-    ctx.prof_sample(every)
-    ctx.prof_enable(True)
-    run.iterate(a.warmup)
-    ctx.prof_enable(True)          # clears the warmup's timings
+    if a.full:
+        # first epoch with every kernel section timed: the breakdown and the dominant section
+        ctx.prof_select(None)
+        ctx.prof_sample(1)
+        ctx.prof_enable(True)
+        run.iterate(wep)
+        breakdown = ctx.prof_read()
+        ctx.prof_enable(False)
+        # the dominant GEMM section (the roofline is a GEMM's); at many ranks the epoch's all-reduce can take
+        # longer, but it runs once or twice per epoch, too rarely to sample
+        gemms = {k: v for k, v in breakdown.items() if k.split("[")[0] in ("gemm_fwd", "gemm_dw", "gemm_dx")}
+        dominant = max((gemms or breakdown).items(), key=lambda kv: kv[1][0])[0]
+        if world > 1:
+            obj = [dominant]
+            torch.distributed.broadcast_object_list(obj, src=0)
+            dominant = obj[0]
+        # timed region: only the dominant section carries events, on every PROF_EVERY-th launch (an event pair
+        # costs ~10 us of GPU time, and this section runs ~2x per inner step) while that still times
+        # PROF_MIN_LAUNCHES of them; the rows of every timed launch are counted (lbf_prof_read_work), so the
+        # sampled flops are exact whatever the batch sizes
+        every = max(1, min(PROF_EVERY, int(breakdown[dominant][1] * max(a.steps, 1) // PROF_MIN_LAUNCHES)))
+        ctx.prof_select(dominant)
+        ctx.prof_sample(every)
+        ctx.prof_enable(True)
+        run.iterate(a.warmup)
+        ctx.prof_enable(True)          # clears the warmup's timings
+    else:
+        # the same untimed epochs as with --full (its breakdown epoch, then the warmup), no events anywhere
+        run.iterate(wep)
+        run.iterate(a.warmup)
+    h0 = run.hist.size
     evals0, rows0, ep0 = float(run.info.n_evals), float(run.info.n_rows), int(run.info.iterations)
     DEV.synchronize()
     if world > 1:
@@ -310,29 +354,15 @@ def main_slbfgs(a, pkg, ctx, world, rank):
         cnt[0] = mx[0]
         torch.distributed.barrier()
     elapsed, evals_all, rows_all = float(cnt[0]), float(cnt[1]), float(cnt[2])
-    prof = ctx.prof_read()
-    work = ctx.prof_read_work()
-    ctx.prof_enable(False)
-    ctx.prof_select(None)
-    ctx.prof_sample(1)
+    if a.full:
+        prof = ctx.prof_read()
+        work = ctx.prof_read_work()
+        ctx.prof_enable(False)
+        ctx.prof_select(None)
+        ctx.prof_sample(1)
     if rank == 0:
         epochs = int(info.iterations) - ep0
         F = pkg.grad_flops_per_sample(dims)
-        if dominant not in prof:
-            raise SystemExit(f"bench.py: the dominant section {dominant} did not run in the timed region")
-        name, (ms, launches) = dominant, prof[dominant]
-        kind, layer = name.split("[")[0], int(name.split("[")[1].rstrip("]"))
-        roof = dict(bound="mfma", achieved=None, peak=FP32_MFMA_PEAK_TFLOPS, unit="TFLOP/s", frac=None)
-        if kind in ("gemm_fwd", "gemm_dw", "gemm_dx"):
-            # algorithmic flops of the timed launches (2 In Out per row, rows counted per launch) / their
-            # summed event time
-            flops = 2.0 * dims[layer] * dims[layer + 1] * float(work.get(dominant, 0.0))
-            roof["achieved"] = round(flops / (ms / 1e3) / 1e12, 3)
-            roof["frac"] = round(roof["achieved"] / roof["peak"], 4)
-        roof.update(kernel=name, avg_launch_us=round(ms * 1e3 / launches, 2), timed_launches=launches,
-                    sampled_every=every, avg_rows_per_timed_launch=round(work.get(dominant, 0.0) / launches, 1),
-                    traffic=pmc_traffic(a.pmc_json, name, f"{','.join(str(d) for d in dims)}:{a.samples}:{world}"))
-        # (traffic: the median over the section's minibatch launches, the PMC pass's most frequent size)
         out = {
             "metric": "S-LBFGS epochs/s + grad-evals/s, 784-512-256-10 MLP",
             "value": round(epochs / elapsed, 4),
@@ -354,12 +384,31 @@ def main_slbfgs(a, pkg, ctx, world, rank):
             "grad_evals_per_s": round(evals_all / elapsed, 1),
             "grad_eval_gflops": round(rows_all * F / elapsed / 1e9, 1),
             "final_loss": float(info.final_loss),
-            "roofline": roof,
-            "kernel_ms_per_step": {k: round(v[0] / wep, 4) for k, v in sorted(breakdown.items())},
             "route_env": route_env(),
         }
-        if world == 1 and not a.no_cpu_baseline:
-            out["cpu_baseline"] = slbfgs_cpu_baseline(dims, acts, N, a.slbfgs_step)
+        if a.full:
+            if dominant not in prof:
+                raise SystemExit(f"bench.py: the dominant section {dominant} did not run in the timed region")
+            name, (ms, launches) = dominant, prof[dominant]
+            kind, layer = name.split("[")[0], int(name.split("[")[1].rstrip("]"))
+            roof = dict(bound="mfma", achieved=None, peak=FP32_MFMA_PEAK_TFLOPS, unit="TFLOP/s", frac=None)
+            if kind in ("gemm_fwd", "gemm_dw", "gemm_dx"):
+                # algorithmic flops of the timed launches (2 In Out per row, rows counted per launch) / their
+                # summed event time
+                flops = 2.0 * dims[layer] * dims[layer + 1] * float(work.get(dominant, 0.0))
+                roof["achieved"] = round(flops / (ms / 1e3) / 1e12, 3)
+                roof["frac"] = round(roof["achieved"] / roof["peak"], 4)
+            # (traffic: the median over the section's minibatch launches, the PMC pass's most frequent size)
+            roof.update(kernel=name, avg_launch_us=round(ms * 1e3 / launches, 2), timed_launches=launches,
+                        sampled_every=every, avg_rows_per_timed_launch=round(work.get(dominant, 0.0) / launches, 1),
+                        traffic=pmc_traffic(a.pmc_json, name,
+                                            f"{','.join(str(d) for d in dims)}:{a.samples}:{world}"))
+            out["roofline"] = roof
+            out["kernel_ms_per_step"] = {k: round(v[0] / wep, 4) for k, v in sorted(breakdown.items())}
+            if world == 1 and not a.no_cpu_baseline:
+                out["cpu_baseline"] = slbfgs_cpu_baseline(dims, acts, N, a.slbfgs_step)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, P, run.hist, h0)
         emit(out)
     run.close()
 
@@ -517,37 +566,41 @@ def run_rank(a, world, rank, local, pkg):
     # untimed pass with every kernel section timed: per-section breakdown and the dominant section. It runs
     # before the W warmup iterations, so that the timed region follows full-speed iterations (the
     # breakdown's event on every launch leaves the chip below its steady clock); the timed iterations are
-    # the same ones either way (the breakdown's + W iterations precede them).
-    ctx.prof_select(None)
-    ctx.prof_enable(True)
+    # the same ones either way (the breakdown's + W iterations precede them). A plain run makes the same
+    # iterations with no events, so that it times the iterations that --full times.
+    if a.full:
+        ctx.prof_select(None)
+        ctx.prof_enable(True)
     bd_steps = max(1, min(a.steps, 20))
     bd0 = run.hist.size
     run.iterate(bd_steps)
-    breakdown = ctx.prof_read()
     bd_steps = max(run.hist.size - bd0, 1)
-    ctx.prof_enable(False)
+    if a.full:
+        breakdown = ctx.prof_read()
+        ctx.prof_enable(False)
     if not a.breakdown_last:
         run.iterate(a.warmup)
-    # the section with the largest total time among those that run at least once per iteration (a section of
-    # the occasional non-speculative start can win the breakdown when a profiler serialises the launches)
-    regular = {k: v for k, v in breakdown.items() if v[1] >= bd_steps} or breakdown
-    # the roofline is a GEMM's: at many ranks the all-reduce section can take longer than any GEMM
-    gemms = {k: v for k, v in regular.items() if k.split("[")[0] in ("gemm_fwd", "gemm_dw", "gemm_dx")}
-    dominant = max((gemms or regular).items(), key=lambda kv: kv[1][0])[0]
-    if world > 1:  # every rank must time the same section (identical launch sequences)
-        obj = [dominant]
-        torch.distributed.broadcast_object_list(obj, src=0)
-        dominant = obj[0]
-    # timed region: only the dominant kernel carries an event pair
     evals0, lonly0, gal0 = run.info.n_evals, run.info.n_loss_only, run.info.n_grad_after_loss
     it0 = run.hist.size
-    ctx.prof_select(dominant)
-    # the dominant section runs about once per evaluation: sample every PROF_EVERY-th launch only when
-    # that still times PROF_MIN_LAUNCHES of them
-    launches = breakdown[dominant][1] / max(bd_steps, 1) * a.steps
-    every = max(1, min(PROF_EVERY, int(launches // PROF_MIN_LAUNCHES)))
-    ctx.prof_sample(every)
-    ctx.prof_enable(True)
+    if a.full:
+        # the section with the largest total time among those that run at least once per iteration (a section
+        # of the occasional non-speculative start can win the breakdown when a profiler serialises the launches)
+        regular = {k: v for k, v in breakdown.items() if v[1] >= bd_steps} or breakdown
+        # the roofline is a GEMM's: at many ranks the all-reduce section can take longer than any GEMM
+        gemms = {k: v for k, v in regular.items() if k.split("[")[0] in ("gemm_fwd", "gemm_dw", "gemm_dx")}
+        dominant = max((gemms or regular).items(), key=lambda kv: kv[1][0])[0]
+        if world > 1:  # every rank must time the same section (identical launch sequences)
+            obj = [dominant]
+            torch.distributed.broadcast_object_list(obj, src=0)
+            dominant = obj[0]
+        # timed region: only the dominant kernel carries an event pair
+        ctx.prof_select(dominant)
+        # the dominant section runs about once per evaluation: sample every PROF_EVERY-th launch only when
+        # that still times PROF_MIN_LAUNCHES of them
+        launches = breakdown[dominant][1] / max(bd_steps, 1) * a.steps
+        every = max(1, min(PROF_EVERY, int(launches // PROF_MIN_LAUNCHES)))
+        ctx.prof_sample(every)
+        ctx.prof_enable(True)
 
     def barrier():
         DEV.synchronize()
@@ -566,11 +619,12 @@ def run_rank(a, world, rank, local, pkg):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     barrier()
-    prof = ctx.prof_read()
-    work = ctx.prof_read_work()
-    ctx.prof_enable(False)
-    ctx.prof_select(None)
-    ctx.prof_sample(1)
+    if a.full:
+        prof = ctx.prof_read()
+        work = ctx.prof_read_work()
+        ctx.prof_enable(False)
+        ctx.prof_select(None)
+        ctx.prof_sample(1)
     evals = run.info.n_evals - evals0
     lonly = run.info.n_loss_only - lonly0
     gal = run.info.n_grad_after_loss - gal0
@@ -583,26 +637,6 @@ def run_rank(a, world, rank, local, pkg):
         # loss-only trial's forward (each counted in n_evals too); backward passes: n_evals
         fwd_passes = evals - gal + lonly
         gflops = (fwd_passes * Ffwd + evals * (F - Ffwd)) / elapsed / 1e9
-        # dominant kernel: largest total time in the timed region (HIP events on the library stream)
-        if dominant not in prof:
-            raise SystemExit(f"bench.py: the dominant section {dominant} did not run in the timed region")
-        name, (ms, cnt) = dominant, prof[dominant]
-        avg_s = ms / 1e3 / cnt
-        kind, layer = name.split("[")[0], int(name.split("[")[1].rstrip("]"))
-        n_loc = hi - lo
-        In, Out = dims[layer], dims[layer + 1]
-        if kind in ("gemm_fwd", "gemm_dw", "gemm_dx"):
-            flops = 2.0 * In * Out * work.get(dominant, n_loc * cnt) / cnt  # per launch (rows counted), per rank
-            roof = dict(bound="mfma", achieved=round(flops / avg_s / 1e12, 3), peak=FP32_MFMA_PEAK_TFLOPS,
-                        unit="TFLOP/s")
-        else:
-            roof = dict(bound="hbm", achieved=None, peak=HBM_PEAK_GBS, unit="GB/s")
-        roof["frac"] = round(roof["achieved"] / roof["peak"], 4) if roof["achieved"] else None
-        roof["kernel"] = name
-        roof["avg_launch_us"] = round(avg_s * 1e6, 2)
-        roof["timed_launches"] = cnt
-        roof["sampled_every"] = every
-        roof["traffic"] = pmc_traffic(a.pmc_json, name, f"{a.dims}:{N}:{world}")
         ms_step = elapsed / max(iters_done, 1) * 1e3
         value = iters_done / elapsed
         out = {
@@ -629,13 +663,36 @@ def run_rank(a, world, rank, local, pkg):
             "evals_per_iter": round(evals / max(iters_done, 1), 3),
             "loss_only_trials_per_iter": round(lonly / max(iters_done, 1), 3),
             "forward_passes_per_iter": round(fwd_passes / max(iters_done, 1), 3),
-            "roofline": roof,
-            "kernel_ms_per_step": {k: round(v[0] / bd_steps, 4) for k, v in sorted(breakdown.items())},
             "route_env": route_env(),
         }
-        if world == 1 and not a.no_cpu_baseline:
-            rows = a.cpu_samples or (N if N <= 60000 else 2000)
-            out["cpu_baseline"] = cpu_baseline(dims, acts, N, a.m, a.cpu_iters, a.data, min(rows, N))
+        if a.full:
+            # dominant kernel: largest total time in the timed region (HIP events on the library stream)
+            if dominant not in prof:
+                raise SystemExit(f"bench.py: the dominant section {dominant} did not run in the timed region")
+            name, (ms, cnt) = dominant, prof[dominant]
+            avg_s = ms / 1e3 / cnt
+            kind, layer = name.split("[")[0], int(name.split("[")[1].rstrip("]"))
+            n_loc = hi - lo
+            In, Out = dims[layer], dims[layer + 1]
+            if kind in ("gemm_fwd", "gemm_dw", "gemm_dx"):
+                flops = 2.0 * In * Out * work.get(dominant, n_loc * cnt) / cnt  # per launch (rows counted), per rank
+                roof = dict(bound="mfma", achieved=round(flops / avg_s / 1e12, 3), peak=FP32_MFMA_PEAK_TFLOPS,
+                            unit="TFLOP/s")
+            else:
+                roof = dict(bound="hbm", achieved=None, peak=HBM_PEAK_GBS, unit="GB/s")
+            roof["frac"] = round(roof["achieved"] / roof["peak"], 4) if roof["achieved"] else None
+            roof["kernel"] = name
+            roof["avg_launch_us"] = round(avg_s * 1e6, 2)
+            roof["timed_launches"] = cnt
+            roof["sampled_every"] = every
+            roof["traffic"] = pmc_traffic(a.pmc_json, name, f"{a.dims}:{N}:{world}")
+            out["roofline"] = roof
+            out["kernel_ms_per_step"] = {k: round(v[0] / bd_steps, 4) for k, v in sorted(breakdown.items())}
+            if world == 1 and not a.no_cpu_baseline:
+                rows = a.cpu_samples or (N if N <= 60000 else 2000)
+                out["cpu_baseline"] = cpu_baseline(dims, acts, N, a.m, a.cpu_iters, a.data, min(rows, N))
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, P, run.hist, it0)
         emit(out)
     run.close()
 

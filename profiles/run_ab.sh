@@ -11,8 +11,8 @@ ok=0
 for rep in 1 2; do
   for v in ab new; do
     L=$AB; [ $v = new ] && L=$NEW
-    LBF_LIB_PATH=$L timeout -k 10 120 python -u bench.py --no-cpu-baseline --steps 300 > $O/b_${v}_$rep.json 2> $O/b_${v}_$rep.err || { ok=1; break 2; }
-    LBF_LIB_PATH=$L timeout -k 10 120 python -u bench.py --samples 7500 --no-cpu-baseline --steps 300 > $O/s_${v}_$rep.json 2> $O/s_${v}_$rep.err || { ok=1; break 2; }
+    LBF_LIB_PATH=$L timeout -k 10 120 python -u bench.py --full --no-cpu-baseline --steps 300 > $O/b_${v}_$rep.json 2> $O/b_${v}_$rep.err || { ok=1; break 2; }
+    LBF_LIB_PATH=$L timeout -k 10 120 python -u bench.py --full --samples 7500 --no-cpu-baseline --steps 300 > $O/s_${v}_$rep.json 2> $O/s_${v}_$rep.err || { ok=1; break 2; }
   done
 done
 [ $ok = 0 ] && for v in ab new; do

@@ -6,7 +6,9 @@
 * the children supervisor: exit code of the job, a failing rank takes the others down;
 * the world-2 control plane of `run_rank` under gloo — RCCL unique-id broadcast, the dominant-section
   broadcast, the barriers around the timed region, the MAX of the ranks' clocks and rank-0-only emission —
-  driven with a host stub of the engine whose per-iteration "all-reduce" is staged through gloo.
+  driven with a host stub of the engine whose per-iteration "all-reduce" is staged through gloo, with
+  `--full` (breakdown, roofline) and as a plain run (neither, no profiling events);
+* `--dump-outputs`: the files it writes and their size bound.
 """
 import json
 import os
@@ -90,6 +92,7 @@ class _Info:
 
 class _Ctx:
     uid_seen = None
+    enabled = 0    # prof_enable(True) calls: a plain run makes none
 
     def __init__(self, dev):
         self.dev = dev
@@ -111,6 +114,7 @@ class _Ctx:
     def prof_enable(self, on):
         self.on = on
         if on:
+            _Ctx.enabled += 1
             self.times, self.work = {}, {}
 
     def prof_read(self):
@@ -207,13 +211,14 @@ def _rank_worker(rank, world, port, outdir, argv):
     wall = time.perf_counter() - t0
     dist.destroy_process_group()
     with open(os.path.join(outdir, f"r{rank}.json"), "w") as f:
-        json.dump(dict(lines=lines, seen=seen, uid=list(_Ctx.uid_seen[2]), wr=_Ctx.uid_seen[:2], wall=wall), f)
+        json.dump(dict(lines=lines, seen=seen, uid=list(_Ctx.uid_seen[2]), wr=_Ctx.uid_seen[:2], wall=wall,
+                       enabled=_Ctx.enabled), f)
 
 
 @pytest.mark.parametrize("solver", ["lbfgs", "slbfgs"])
 def test_control_plane_world2_gloo(solver):
     world, port = 2, bench.free_port()
-    argv = ["--gpus", "2", "--steps", "12", "--warmup", "2", "--samples", "600", "--solver", solver]
+    argv = ["--gpus", "2", "--steps", "12", "--warmup", "2", "--samples", "600", "--solver", solver, "--full"]
     with tempfile.TemporaryDirectory() as d:
         mp.spawn(_rank_worker, args=(world, port, d, argv), nprocs=world, join=True)
         r = [json.load(open(os.path.join(d, f"r{i}.json"))) for i in range(world)]
@@ -236,3 +241,53 @@ def test_control_plane_world2_gloo(solver):
         assert line["steps"] == 12
     else:
         assert r[0]["seen"]["rows"] == 600  # S-LBFGS: every rank holds all rows, evaluates its slice
+
+
+@pytest.mark.parametrize("solver", ["lbfgs", "slbfgs"])
+def test_plain_run_world2_gloo(solver):
+    """Without --full: the same line from rank 0 minus the breakdown, the roofline and the CPU baseline, no
+    profiling events enabled on any rank, and the timed steps are the ones --steps asks for."""
+    world, port = 2, bench.free_port()
+    argv = ["--gpus", "2", "--steps", "12", "--warmup", "2", "--samples", "600", "--solver", solver]
+    with tempfile.TemporaryDirectory() as d:
+        mp.spawn(_rank_worker, args=(world, port, d, argv), nprocs=world, join=True)
+        r = [json.load(open(os.path.join(d, f"r{i}.json"))) for i in range(world)]
+    assert len(r[0]["lines"]) == 1 and r[1]["lines"] == []
+    assert r[0]["enabled"] == 0 and r[1]["enabled"] == 0
+    line = r[0]["lines"][0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "config"):
+        assert k in line
+    for k in ("roofline", "kernel_ms_per_step", "cpu_baseline"):
+        assert k not in line
+    assert line["steps"] == 12 and line["warmup"] == 2 and line["n_gpus"] == 2
+    assert line["ms_per_step"] >= 10.0      # the slow rank's clock, as with --full
+    assert abs(line["value"] * line["ms_per_step"] - 1e3) <= 1.0   # value = steps/s, ms_per_step = ms per step
+
+
+def test_options_full_and_dump_outputs():
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out", "--steps", "7"])
+    assert a.full is True and a.dump_outputs == "out" and a.steps == 7
+
+
+def test_dump_outputs_files_and_budget(tmp_path, monkeypatch):
+    """dump_outputs: the timed steps' record rows as float64, the parameters as float32, and a seeded,
+    repeatable sample where an array exceeds its share of the budget."""
+    hist = types.SimpleNamespace(size=9, loss=np.arange(12.0), grad_norm=np.arange(12.0) * 2, alpha=np.ones(12),
+                                 ls_trials=np.arange(12, dtype=np.int32), accepted=np.ones(12, np.int32))
+    P = torch.arange(5000, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "a"), P, hist, 4)
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["accepted.npy", "alpha.npy", "grad_norm.npy", "loss.npy", "ls_trials.npy", "params.npy"]
+    assert got["params.npy"].dtype == np.float32 and np.array_equal(got["params.npy"], P.numpy())
+    assert got["loss.npy"].dtype == np.float64 and np.array_equal(got["loss.npy"], np.arange(4.0, 9.0))
+    assert got["ls_trials.npy"].dtype == np.float64 and np.array_equal(got["ls_trials.npy"], np.arange(4.0, 9.0))
+    # five record columns of 40 bytes, 4096 allowed for each file's header: 4000 bytes are left for the parameters
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 5 * (40 + 4096) + 4096 + 4000)
+    for name in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / name), P, hist, 4)
+    pb, pc = np.load(tmp_path / "b" / "params.npy"), np.load(tmp_path / "c" / "params.npy")
+    assert pb.size == 1000 and np.array_equal(pb, pc) and np.all(np.diff(pb) > 0)
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= bench.DUMP_BUDGET_BYTES
