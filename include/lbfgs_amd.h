@@ -135,6 +135,20 @@ int lbf_mlp_loss(lbf_mlp *net, const float *d_params, const float *d_X, const fl
  * (two fused batch evaluations; the fp32 difference times the once-rounded 1/(2 eps)). */
 int lbf_mlp_fd_hvp(lbf_mlp *net, const float *d_params, const float *d_v, const float *d_X, const float *d_Y,
                    const int *d_idx, long long batch, double inv_scale, double l2, double eps, float *d_y);
+/* The loss of the network (extension; the reference has the squared error only). LBF_LOSS_MSE (the default) is
+ * the loss documented above. LBF_LOSS_SOFTMAX_XENT: the network's outputs z are logits (the last layer's
+ * activation must be LBF_ACT_LINEAR and it must have at least two outputs, else LBF_ERR_INVALID), and with
+ * lse_b = log sum_o exp(z_bo)
+ *   loss = inv_scale * sum_b sum_o y_bo (lse_b - z_bo) + 0.5*l2*||w||^2        (no factor 0.5)
+ * for target rows y_b >= 0 (one-hot or soft; not validated). inv_scale, l2, d_idx, sharding and n_global keep
+ * their meaning. It is a property of the network: lbf_mlp_loss_grad, lbf_mlp_loss, lbf_mlp_hvp, lbf_mlp_fd_hvp,
+ * lbf_mlp_batch_grads and every solver created on the network minimise it; lbf_mlp_forward returns the logits.
+ * Takes effect from the next evaluation / solve. Must not be changed between *_begin and *_end of a stateful
+ * solver (its history and recorded losses would mix two objectives). */
+#define LBF_LOSS_MSE 0
+#define LBF_LOSS_SOFTMAX_XENT 1
+int lbf_mlp_set_loss(lbf_mlp *net, int loss);
+int lbf_mlp_get_loss(const lbf_mlp *net, int *loss);
 int lbf_two_loop(lbf_ctx *ctx, long long n, int k, const float *d_S, const float *d_Y, const double *h_rho,
                  const float *d_g, float *d_dir, int mode);
 

@@ -59,6 +59,10 @@ struct Tanh { static constexpr int id = LBF_ACT_TANH; };
 struct ReLU { static constexpr int id = LBF_ACT_RELU; };
 struct Sigmoid { static constexpr int id = LBF_ACT_SIGMOID; };
 
+/// The loss the network's evaluations and every solver on it minimise (lbf_mlp_set_loss; an extension: the
+/// reference has the squared error only). SoftmaxCrossEntropy takes the outputs of a Linear last layer as logits.
+enum class Loss : int { MeanSquaredError = LBF_LOSS_MSE, SoftmaxCrossEntropy = LBF_LOSS_SOFTMAX_XENT };
+
 /// Maps an activation tag type to the engine's id; specialise for other tag types.
 template <typename T> struct ActivationId { static constexpr int value = T::id; };
 
@@ -141,9 +145,17 @@ public:
       hip_check(lbf_mlp_create(h_.get(), int(acts_.size()), dims_.data(), acts_.data(), &net_), "lbf_mlp_create");
       params_.resize(size_t(lbf_mlp_param_count(net_)));
       grads_.resize(params_.size());
+      if (loss_ != Loss::MeanSquaredError) hip_check(lbf_mlp_set_loss(net_, int(loss_)), "lbf_mlp_set_loss");
     }
     hip_check(lbf_mlp_init_params(net_, seed, init_mode, params_.data()), "lbf_mlp_init_params");
   }
+  /// Before or after bindParams(); not between a stateful solver's begin and end. An invalid choice (a
+  /// non-linear last layer, fewer than two outputs) aborts like any engine error.
+  void setLoss(Loss loss) {
+    if (net_) hip_check(lbf_mlp_set_loss(net_, int(loss)), "lbf_mlp_set_loss");
+    loss_ = loss;
+  }
+  Loss loss() const { return loss_; }
   size_t params_size() const { return params_.size(); }
   int output_size() const { return dims_.empty() ? 0 : dims_.back(); }
   HipScalar *params_data() { return params_.data(); }
@@ -151,7 +163,7 @@ public:
   void forward_only(const HipScalar *input, int batch, HipScalar *out) {
     hip_check(lbf_mlp_forward(net_, params_.data(), input, batch, out), "lbf_mlp_forward");
   }
-  /// Mean MSE loss and gradient into grads_data() (network.cuh:97-119).
+  /// Mean loss (MSE, or the cross-entropy after setLoss) and gradient into grads_data() (network.cuh:97-119).
   HipScalar compute_loss_and_grad(const HipScalar *input, const HipScalar *target, int batch) {
     double loss = 0.0;
     hip_check(lbf_mlp_loss_grad(net_, params_.data(), grads_.data(), input, target, nullptr, batch, 1.0 / batch, 0.0,
@@ -167,6 +179,7 @@ private:
   HipHandle &h_;
   lbf_mlp *net_ = nullptr;
   std::vector<int> dims_, acts_;
+  Loss loss_ = Loss::MeanSquaredError;
   DeviceBuffer<HipScalar> params_, grads_;
 };
 
@@ -533,6 +546,9 @@ public:
         d_test_y_(handle_) {}
   template <int In, int Out, typename Activation> void addLayer() { net_wrapper_.addLayer<In, Out, Activation>(); }
   void buildNetwork() { net_wrapper_.bindParams(); }
+  /// The loss train() minimises and evaluate() reports (default: the reference's MSE). It lives on the network,
+  /// not in UnifiedConfig, which in reference mode is the reference's own struct.
+  void setLoss(hip_mlp::Loss loss) { net_wrapper_.getInternal().setLoss(loss); }
 
   /// Host -> device upload with the fp64 -> fp32 conversion of unified_launcher.hpp:105-128; like the reference
   /// it keeps a copy of the dataset, which train() hands to the strategy as host_data.
@@ -580,7 +596,8 @@ private:
     net.forward_only(d_x.data(), int(batch), d_out.data());
     std::vector<hip_mlp::HipScalar> out(size_t(batch) * out_dim);
     d_out.copy_to_host(out.data(), out.size());
-    double mse = 0.0;
+    const bool xent = net.loss() == hip_mlp::Loss::SoftmaxCrossEntropy;
+    double mse = 0.0; // with the cross-entropy loss: the mean cross-entropy per sample, under the same label
     long correct = 0;
     for (long i = 0; i < batch; ++i) {
       int pi = 0, ti = 0;
@@ -588,13 +605,19 @@ private:
       for (int r = 0; r < out_dim; ++r) {
         const size_t idx = size_t(r + i * out_dim);
         const double v = out[idx], t = y[idx];
-        mse += (v - t) * (v - t);
+        if (!xent) mse += (v - t) * (v - t);
         if (v > pm) { pm = v; pi = r; }
         if (t > tm) { tm = t; ti = r; }
       }
+      if (xent) { // sum_o y (lse - z), lse from the row maximum pm
+        double se = 0.0;
+        for (int r = 0; r < out_dim; ++r) se += std::exp(double(out[size_t(r + i * out_dim)]) - pm);
+        const double lse = pm + std::log(se);
+        for (int r = 0; r < out_dim; ++r) mse += y[size_t(r + i * out_dim)] * (lse - out[size_t(r + i * out_dim)]);
+      }
       if (pi == ti) ++correct;
     }
-    mse /= double(batch * out_dim);
+    mse /= xent ? double(batch) : double(batch * out_dim);
     const double acc = double(correct) / double(batch) * 100.0;
     std::cout << label << ": MSE=" << mse << ", Accuracy=" << acc << "%" << std::endl;
     return {mse, acc};

@@ -7,7 +7,7 @@ The directory name contains a hyphen, so load it with :func:`load` from the repo
 """
 from ._lib import LIB_PATH, LbfError, lib  # noqa: F401
 from .engine import (Context, History, LbfgsRun, Mlp, SlbfgsRun, gd_solve, grad_flops_per_sample, init_params_host,  # noqa: F401
-                     lbfgs_solve, load_idx_images, load_idx_labels, sample_indices, sgd_solve, slbfgs_solve,
+                     lbfgs_solve, lbfgs_solve_fn, load_idx_images, load_idx_labels, sample_indices, sgd_solve, slbfgs_solve,
                      synth_mnist, synth_regression)
 from .unified import (IterationRecorder, UnifiedConfig, UnifiedDataset, UnifiedGD, UnifiedLauncher,  # noqa: F401
                       UnifiedLBFGS, UnifiedSGD, UnifiedSLBFGS, write_history_csv)

@@ -20,6 +20,7 @@ SLBFGS_DP_REPLICATED, SLBFGS_DP_SLICED = 0, 1
 LS_WOLFE, LS_ARMIJO = 0, 1
 INIT_CPU, INIT_CUDA = 0, 1
 ACTS = {"linear": 0, "tanh": 1, "relu": 2, "sigmoid": 3}
+LOSSES = {"mse": 0, "softmax_xent": 1}  # LBF_LOSS_MSE, LBF_LOSS_SOFTMAX_XENT
 
 
 class LbfError(RuntimeError):
@@ -140,6 +141,8 @@ def lib():
         "lbf_sgd_solve": (C.c_int, [_vp, C.POINTER(SgdParams), _vp, _vp, _vp, C.c_longlong, C.POINTER(Record),
                                     C.POINTER(SolveInfo)]),
         "lbf_synth_regression": (C.c_int, [_vp, C.c_longlong, C.c_longlong, C.c_int, C.c_uint, C.c_uint, _vp, _vp]),
+        "lbf_mlp_set_loss": (C.c_int, [_vp, C.c_int]),
+        "lbf_mlp_get_loss": (C.c_int, [_vp, _ip]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -157,7 +160,8 @@ EXPORTS = ("lbf_last_error lbf_version lbf_abi_version lbf_ctx_create lbf_ctx_de
            "lbf_nrm2 lbf_axpy lbf_scal lbf_lbfgs_default_params lbf_slbfgs_default_params lbf_lbfgs_solve "
            "lbf_lbfgs_begin lbf_lbfgs_iterate lbf_lbfgs_end lbf_lbfgs_solve_fn lbf_device_alloc lbf_device_free lbf_memcpy lbf_slbfgs_solve lbf_slbfgs_begin lbf_slbfgs_iterate lbf_slbfgs_end lbf_slbfgs_pair0 lbf_slbfgs_pair_io lbf_prof_enable lbf_prof_select lbf_prof_sample lbf_prof_read lbf_prof_read_work lbf_synth_mnist "
            "lbf_sample_indices lbf_synth_regression lbf_gd_default_params lbf_sgd_default_params lbf_gd_solve "
-           "lbf_sgd_solve lbf_idx_read_images lbf_idx_read_labels lbf_mlp_hvp lbf_mlp_fd_hvp lbf_mlp_loss").split()
+           "lbf_sgd_solve lbf_idx_read_images lbf_idx_read_labels lbf_mlp_hvp lbf_mlp_fd_hvp lbf_mlp_loss "
+           "lbf_mlp_set_loss lbf_mlp_get_loss").split()
 
 
 def check(rc: int, what: str) -> None:

@@ -282,6 +282,21 @@ int lbf_mlp_hvp(lbf_mlp *net, const float *d_params, const float *d_v, const flo
   });
 }
 
+int lbf_mlp_set_loss(lbf_mlp *net, int loss) {
+  return guard([&] {
+    LBF_REQUIRE(net, "null argument");
+    static_assert(LBF_LOSS_MSE == LOSS_MSE && LBF_LOSS_SOFTMAX_XENT == LOSS_XENT, "loss codes");
+    net->net->set_loss(loss);
+  });
+}
+
+int lbf_mlp_get_loss(const lbf_mlp *net, int *loss) {
+  return guard([&] {
+    LBF_REQUIRE(net && loss, "null argument");
+    *loss = net->net->loss();
+  });
+}
+
 int lbf_mlp_fd_hvp(lbf_mlp *net, const float *d_params, const float *d_v, const float *d_X, const float *d_Y,
                    const int *d_idx, long long batch, double inv_scale, double l2, double eps, float *d_y) {
   return guard([&] {

@@ -329,7 +329,7 @@ template <int WM, int WN, int TM, int TN, int EPI, int KW, class HPre>
 __device__ __forceinline__ void gemm_epilogue(const GemmK &g, f32x16 (&acc)[TM][TN], float *lds, HPre &hpre, int zsplit,
                                               int m0, int n0, int wm, int wn, int li, int lh, int kgrp) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-  if constexpr (EPI == EPI_HEAD) {
+  if constexpr (epi_head(EPI)) {
     KTB(1);
     // Output layer on the tile (head_core.hpp): the prefetched W / biases / targets go to LDS, then per
     // 64-row half the activations go accumulators -> LDS (bias + activation; columns >= N zero) and
@@ -405,8 +405,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmK &g, f32x16 (&acc)[TM][
       lds_barrier();
       KT(28 + 2 * half);
       KTB(3 + 2 * half);
-      if (fold) headc::tile<(KW > 1), QM, true, TBR>(hs, ta, b0, rows, cw, sse, fa);
-      else headc::tile<(KW > 1), QM, false, TBR>(hs, ta, b0, rows, cw, sse, fa);
+      constexpr int LOSS = EPI == EPI_HEAD_XENT ? LOSS_XENT : LOSS_MSE;
+      if (fold) headc::tile<(KW > 1), QM, true, TBR, LOSS>(hs, ta, b0, rows, cw, sse, fa);
+      else headc::tile<(KW > 1), QM, false, TBR, LOSS>(hs, ta, b0, rows, cw, sse, fa);
       KT(29 + 2 * half);
       KTB(4 + 2 * half);
     }
@@ -469,7 +470,7 @@ __global__ __launch_bounds__(256 * KW, 2) void gemm_kernel(const GemmK g) {
   constexpr int ASZ = AKC ? BM * LDK : BK * (BM + 4);
   constexpr int BSZ = BKC ? BN * LDK : BK * (BN + 4);
   constexpr int HEAD_F = headc::smem_floats_epi(BN, BM > headc::TB ? BM : headc::TB);
-  constexpr int LDS_F = (EPI == EPI_HEAD && HEAD_F > 2 * (ASZ + BSZ)) ? HEAD_F : 2 * (ASZ + BSZ);
+  constexpr int LDS_F = (epi_head(EPI) && HEAD_F > 2 * (ASZ + BSZ)) ? HEAD_F : 2 * (ASZ + BSZ);
   __shared__ __attribute__((aligned(16))) float lds[LDS_F];
   if (g.early.sse_part ? gemm_early_exit(g, lds) : (g.abort && *g.abort)) return;
   if (int(blockIdx.z) < g.side_planes) {
@@ -595,14 +596,14 @@ __global__ __launch_bounds__(256 * KW, 2) void gemm_kernel(const GemmK g) {
     }
   };
 
-  if (EPI == EPI_HEAD) KT(0);
-  if (EPI == EPI_HEAD) KTB(0);
-  if (EPI == EPI_HEAD) KTHW();
+  if (epi_head(EPI)) KT(0);
+  if (epi_head(EPI)) KTB(0);
+  if (epi_head(EPI)) KTHW();
   // EPI_HEAD: the head's HBM inputs (W, biases, targets) are loaded while the last k-tile computes
   headc::EpiPrefetch<BN, BM, 256 * KW> hpre;
   if (kb < ke) {
     const int nk = (ke - kb + BK - 1) / BK;
-    const int nloop = EPI == EPI_HEAD ? nk - 1 : nk; // EPI_HEAD peels the last k-tile
+    const int nloop = epi_head(EPI) ? nk - 1 : nk; // EPI_HEAD peels the last k-tile
     // register set p holds k-tile i with i % PF == p; LDS buffer i & 1 holds k-tile i while computed
 #pragma unroll
     for (int p = 0; p < PF; ++p)
@@ -619,17 +620,17 @@ __global__ __launch_bounds__(256 * KW, 2) void gemm_kernel(const GemmK g) {
         compute(i & 1);
         if (i + 1 < nk) sstore(ra[(u + 1) % PF], rb[(u + 1) % PF], (i + 1) & 1, kb + (i + 1) * BK);
         __syncthreads();
-        if (EPI == EPI_HEAD && i < 24) KT(1 + i);
+        if (epi_head(EPI) && i < 24) KT(1 + i);
       }
     }
-    if constexpr (EPI == EPI_HEAD) {
+    if constexpr (epi_head(EPI)) {
       hpre.load(g.head_P, g.N, g.head_out, g.bias, g.head_Y, g.head_idx, m0, g.M);
       if (g.head_fold > 0) hpre.load_fold(g.A, g.lda, g.a_idx, g.head_fold_c0, g.head_fold, m0, g.M);
       compute((nk - 1) & 1);
       __syncthreads();
       KT(25);
     }
-  } else if constexpr (EPI == EPI_HEAD) {
+  } else if constexpr (epi_head(EPI)) {
     hpre.load(g.head_P, g.N, g.head_out, g.bias, g.head_Y, g.head_idx, m0, g.M);
     if (g.head_fold > 0) hpre.load_fold(g.A, g.lda, g.a_idx, g.head_fold_c0, g.head_fold, m0, g.M);
   }
@@ -709,7 +710,7 @@ template <int WM, int WN, int TM, int TN, int EPI, int NS> struct GldsShape {
   static constexpr int BM = WM * TM * 32, BN = WN * TN * 32, BK = 32;
   static constexpr int STG = (BM + BN) * BK;
   static constexpr int HEAD_F = headc::smem_floats_epi(BN, BM > headc::TB ? BM : headc::TB);
-  static constexpr int LDS_F = (EPI == EPI_HEAD && HEAD_F > NS * STG) ? HEAD_F : NS * STG;
+  static constexpr int LDS_F = (epi_head(EPI) && HEAD_F > NS * STG) ? HEAD_F : NS * STG;
 };
 
 // One GEMM tile (bx, by) of split zsplit (the kernels below choose the problem and the tile).
@@ -853,12 +854,12 @@ __device__ __forceinline__ void glds_body(const GemmK &g, float *lds, int zsplit
     mfma_frag(f);
   };
 
-  if (EPI == EPI_HEAD) KT(0);
-  if (EPI == EPI_HEAD) KTC(40);
-  if (EPI == EPI_HEAD) KTB(0);
-  if (EPI == EPI_HEAD) KTHW();
+  if (epi_head(EPI)) KT(0);
+  if (epi_head(EPI)) KTC(40);
+  if (epi_head(EPI)) KTB(0);
+  if (epi_head(EPI)) KTHW();
   headc::EpiPrefetch<BN, BM, 256 * KW> hpre;
-  if constexpr (EPI == EPI_HEAD) {
+  if constexpr (epi_head(EPI)) {
     hpre.load(g.head_P, g.N, g.head_out, g.bias, g.head_Y, g.head_idx, m0, g.M);
     if (g.head_fold > 0) hpre.load_fold(g.A, g.lda, g.a_idx, g.head_fold_c0, g.head_fold, m0, g.M);
   }
@@ -905,13 +906,13 @@ __device__ __forceinline__ void glds_body(const GemmK &g, float *lds, int zsplit
       vm_wait_tiles<PD, NS>(min(NS - 2, nk - 1 - i)); // this wave's pieces of k-tile i landed
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier(); // everyone's pieces landed; buffer (i - 1) % NS no longer read
-      if (EPI == EPI_HEAD && i < 24) KT(1 + i);
+      if (epi_head(EPI) && i < 24) KT(1 + i);
       if (i + NS - 1 < nk) issue(i + NS - 1);
       compute(i % NS);
     }
   }
-  if (EPI == EPI_HEAD) KT(25);
-  if (EPI == EPI_HEAD) KTC(41);
+  if (epi_head(EPI)) KT(25);
+  if (epi_head(EPI)) KTC(41);
   __syncthreads(); // the LDS is the epilogue's now
   if constexpr (KW > 1) { // group sums through LDS, in group order (group 0 keeps the result)
     float *red = lds;
@@ -1021,7 +1022,7 @@ __global__ __launch_bounds__(256, 1) void gemm_wsk_kernel(const GemmK g) {
   const int kb = zsplit * g.k_chunk;
   const int ke = min(g.K, kb + g.k_chunk);
   headc::EpiPrefetch<BN, BM, 256> hpre;
-  if constexpr (EPI == EPI_HEAD) {
+  if constexpr (epi_head(EPI)) {
     hpre.load(g.head_P, g.N, g.head_out, g.bias, g.head_Y, g.head_idx, m0, g.M);
     if (g.head_fold > 0) hpre.load_fold(g.A, g.lda, g.a_idx, g.head_fold_c0, g.head_fold, m0, g.M);
   }
@@ -1278,7 +1279,7 @@ template <bool AKC, bool BKC, int EPI> void dispatch_tile(hipStream_t s, const G
         GemmK k = make_gemmk<32, 128>(d);
         const dim3 grid(unsigned(k.gx), unsigned(k.gy), unsigned((d.splits > 1 ? d.splits : 1) + k.side_planes));
         if (d.a_slab) {
-          if constexpr (!BKC && EPI != EPI_HEAD && EPI != EPI_DX)
+          if constexpr (!BKC && !epi_head(EPI) && EPI != EPI_DX)
             hipLaunchKernelGGL((gemm_wsk_kernel<EPI, false, false, true>), grid, dim3(256), 0, s, k);
         } else if (d.a_idx) {
           hipLaunchKernelGGL((gemm_wsk_kernel<EPI, true, BKC, false>), grid, dim3(256), 0, s, k);
@@ -1374,7 +1375,13 @@ void gemm(hipStream_t s, const GemmDesc &d) {
         (d.N > 128 || d.head_fold > headc::FOLD_MAX || d.head_fold % 4 || d.head_fold_c0 % 4 || d.lda % 4 ||
          d.head_fold_c0 + d.head_fold != d.K || !aligned16(d.A)))
       throw std::runtime_error("gemm: EPI_HEAD fold needs N <= 128, <= 16 aligned input columns ending at K");
-    dispatch_tile<true, false, EPI_HEAD>(s, d);
+    if (d.head_loss == LOSS_XENT) {
+      if (d.head_act != ACT_LINEAR || d.head_out < 2)
+        throw std::runtime_error("gemm: the cross-entropy head needs a linear output layer with Out >= 2");
+      dispatch_tile<true, false, EPI_HEAD_XENT>(s, d);
+    } else {
+      dispatch_tile<true, false, EPI_HEAD>(s, d);
+    }
   } else if (d.epi == EPI_FWD && d.a_kc && !d.b_kc) dispatch_tile<true, false, EPI_FWD>(s, d);
   else if (d.epi == EPI_DX && d.a_kc && d.b_kc) dispatch_tile<true, true, EPI_DX>(s, d);
   else if (d.epi == EPI_STORE && !d.a_kc && !d.b_kc) dispatch_tile<false, false, EPI_STORE>(s, d);

@@ -95,7 +95,7 @@ struct WRegs {
   }
 };
 
-template <int QM>
+template <int QM, int LOSS>
 __global__ __launch_bounds__(256) void head_kernel(const float *A, int H, const float *P, int Out, const float *Y,
                                                    const int *idx, long long B, int act_out, int act_prev,
                                                    double inv_scale, float *delta, float *slab, double *sse_part,
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float *A, int H, const 
     if (vec) lds_barrier();
     else __syncthreads();
     KT(32);
-    tile<false, QM, false>(sm, ta, b0, rows, cw, sse, fa, hr);
+    tile<false, QM, false, TB, LOSS>(sm, ta, b0, rows, cw, sse, fa, hr);
   }
   if (hs != 0) sse = 0.0; // every split computed the same loss; the first one reports it
   write_partials(sm, Out, cw, sse, slab + (long long)blockIdx.x * (H + 1) * Out, sse_part + blockIdx.x, hr);
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float *A, int H, const 
 // lane holds the row's dZ), delta = (dZ W^T) .* act_prev'(a) stored, and the row's [a | 1]^T dZ added into
 // the wave's LDS partial (fp32, row order: what a register accumulator would hold); at the end the four
 // waves' partials are summed in wave order into the block's slab.
-template <int NJ, int OP>
+template <int NJ, int OP, int LOSS>
 __global__ __launch_bounds__(256) void rowhead_kernel(const RowHeadArgs a) {
   if (a.abort && *a.abort) return;
   KT(40);
@@ -307,23 +307,55 @@ __global__ __launch_bounds__(256) void rowhead_kernel(const RowHeadArgs a) {
     });
     // ---- Z = a W + b (fp64 partials, fixed DPP tree), loss, dZ: identical on every lane ----
     float dz[OP];
-    with_act(a.act_out, [&](auto AC) __attribute__((always_inline)) {
-      constexpr int A = decltype(AC)::value;
+    if constexpr (LOSS == LOSS_XENT) {
+      // softmax cross-entropy on the row's logits, serially over the outputs (every lane holds them all)
+      float zv[OP], m = -INFINITY, se = 0.0f, ysum = 0.0f;
 #pragma unroll
       for (int o = 0; o < OP; ++o) {
-        dz[o] = 0.0f;
+        zv[o] = 0.0f;
         if (o < Out) { // uniform
           double zp = 0.0;
 #pragma unroll
           for (int j = 0; j < NJ; ++j) zp += double(av[j]) * double(w2[j][o]);
-          const float z = float(wave_sum_f64(zp));
-          const float outv = act_c<A>(z + b2[o]);
-          const float d = outv - yv[o];
-          sse += double(d) * double(d);
-          dz[o] = d * dact_c<A>(outv) * float(a.inv_scale);
+          zv[o] = float(wave_sum_f64(zp)) + b2[o];
+          m = fmaxf(m, zv[o]);
         }
       }
-    });
+#pragma unroll
+      for (int o = 0; o < OP; ++o) {
+        dz[o] = 0.0f;
+        if (o < Out) {
+          dz[o] = expf(zv[o] - m);
+          se += dz[o];
+          ysum += yv[o];
+        }
+      }
+      const float lg = logf(se), rs = 1.0f / se;
+#pragma unroll
+      for (int o = 0; o < OP; ++o)
+        if (o < Out) {
+          sse += 2.0 * double(yv[o]) * double((m - zv[o]) + lg);
+          dz[o] = (dz[o] * rs * ysum - yv[o]) * float(a.inv_scale);
+        }
+    } else {
+      with_act(a.act_out, [&](auto AC) __attribute__((always_inline)) {
+        constexpr int A = decltype(AC)::value;
+#pragma unroll
+        for (int o = 0; o < OP; ++o) {
+          dz[o] = 0.0f;
+          if (o < Out) { // uniform
+            double zp = 0.0;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) zp += double(av[j]) * double(w2[j][o]);
+            const float z = float(wave_sum_f64(zp));
+            const float outv = act_c<A>(z + b2[o]);
+            const float d = outv - yv[o];
+            sse += double(d) * double(d);
+            dz[o] = d * dact_c<A>(outv) * float(a.inv_scale);
+          }
+        }
+      });
+    }
     KT(44);
     // ---- delta = (dZ W^T) .* act_prev'(a), [dW ; db] += [a | 1]^T dZ ----
     with_act(a.act_prev, [&](auto AC) __attribute__((always_inline)) {
@@ -392,28 +424,32 @@ int rowhead_nwg(long long B) { return int(cdiv(std::max(1LL, B), 4LL * rowhead_r
 
 void rowhead(hipStream_t s, const RowHeadArgs &a) {
   LBF_REQUIRE(rowhead_supported(a.H, a.Out) && a.splits >= 1 && a.rpw == rowhead_rpw(a.B), "rowhead: shape");
+  LBF_REQUIRE(a.loss == LOSS_MSE || (a.loss == LOSS_XENT && a.act_out == ACT_LINEAR && a.Out >= 2),
+              "rowhead: the cross-entropy head needs a linear output layer with Out >= 2");
   const size_t shmem = size_t(5) * (a.H + 1) * a.Out * sizeof(float); // 4 wave partials + [W ; b]
   const int nj = (a.H + 63) / 64, op = (a.Out + 3) / 4 * 4;
   const dim3 grid(unsigned(rowhead_nwg(a.B))), block(256);
   // <NJ, OP> for hidden widths up to 256 and outputs up to 16; the attribute once per instance (thread-safe)
-#define LBF_ROWHEAD_CASE(NJ, OP)                                                                              \
-  if (nj == NJ && op == OP) {                                                                                \
+#define LBF_ROWHEAD_CASE(NJ, OP, LOSS)                                                                        \
+  if (nj == NJ && op == OP && a.loss == LOSS) {                                                              \
     static const bool attr_set = [] {                                                                        \
-      LBF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(rowhead_kernel<NJ, OP>),                    \
+      LBF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(rowhead_kernel<NJ, OP, LOSS>),              \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));                   \
       return true;                                                                                           \
     }();                                                                                                     \
     (void)attr_set;                                                                                          \
-    hipLaunchKernelGGL((rowhead_kernel<NJ, OP>), grid, block, shmem, s, a);                                  \
+    hipLaunchKernelGGL((rowhead_kernel<NJ, OP, LOSS>), grid, block, shmem, s, a);                            \
     LBF_KERNEL_CHECK();                                                                                      \
     return;                                                                                                  \
   }
-#define LBF_ROWHEAD_NJ(NJ) LBF_ROWHEAD_CASE(NJ, 4) LBF_ROWHEAD_CASE(NJ, 8) LBF_ROWHEAD_CASE(NJ, 12) LBF_ROWHEAD_CASE(NJ, 16)
+#define LBF_ROWHEAD_OP(NJ, OP) LBF_ROWHEAD_CASE(NJ, OP, LOSS_MSE) LBF_ROWHEAD_CASE(NJ, OP, LOSS_XENT)
+#define LBF_ROWHEAD_NJ(NJ) LBF_ROWHEAD_OP(NJ, 4) LBF_ROWHEAD_OP(NJ, 8) LBF_ROWHEAD_OP(NJ, 12) LBF_ROWHEAD_OP(NJ, 16)
   LBF_ROWHEAD_NJ(1)
   LBF_ROWHEAD_NJ(2)
   LBF_ROWHEAD_NJ(3)
   LBF_ROWHEAD_NJ(4)
 #undef LBF_ROWHEAD_NJ
+#undef LBF_ROWHEAD_OP
 #undef LBF_ROWHEAD_CASE
   throw Error(2, "rowhead: no instance for this shape");
 }
@@ -438,22 +474,30 @@ int head_nwg(long long B, int H) {
 
 void head_fused(hipStream_t s, const float *A, int H, const float *P, int Out, const float *Y, const int *idx,
                 long long B, int act_out, int act_prev, double inv_scale, float *delta, float *slab,
-                double *sse_part, const int *abort) {
+                double *sse_part, const int *abort, int loss) {
+  LBF_REQUIRE(loss == LOSS_MSE || (loss == LOSS_XENT && act_out == ACT_LINEAR && Out >= 2),
+              "head: the cross-entropy head needs a linear output layer with Out >= 2");
   const size_t shmem = size_t(smem_floats(H)) * sizeof(float);
   // once per process, thread-safe (rank threads of an in-process group launch concurrently)
   static const bool attr_set = [] {
-    const void *fns[] = {reinterpret_cast<const void *>(head_kernel<1>), reinterpret_cast<const void *>(head_kernel<2>),
-                         reinterpret_cast<const void *>(head_kernel<3>), reinterpret_cast<const void *>(head_kernel<4>),
-                         reinterpret_cast<const void *>(head_kernel<5>)};
+#define LBF_HEAD_FNS(Q) \
+  reinterpret_cast<const void *>(head_kernel<Q, LOSS_MSE>), reinterpret_cast<const void *>(head_kernel<Q, LOSS_XENT>)
+    const void *fns[] = {LBF_HEAD_FNS(1), LBF_HEAD_FNS(2), LBF_HEAD_FNS(3), LBF_HEAD_FNS(4), LBF_HEAD_FNS(5)};
+#undef LBF_HEAD_FNS
     for (const void *f : fns)
       LBF_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
     return true;
   }();
   (void)attr_set;
   const dim3 grid(head_nwg(B, H)), block(256);
+#define LBF_HEAD_LAUNCH_L(Q, LOSS)                                                                            \
+  hipLaunchKernelGGL((head_kernel<Q, LOSS>), grid, block, shmem, s, A, H, P, Out, Y, idx, B, act_out, act_prev,    \
+                     inv_scale, delta, slab, sse_part, abort)
 #define LBF_HEAD_LAUNCH(Q)                                                                                    \
-  hipLaunchKernelGGL(head_kernel<Q>, grid, block, shmem, s, A, H, P, Out, Y, idx, B, act_out, act_prev, inv_scale, \
-                     delta, slab, sse_part, abort)
+  do {                                                                                                        \
+    if (loss == LOSS_XENT) LBF_HEAD_LAUNCH_L(Q, LOSS_XENT);                                                   \
+    else LBF_HEAD_LAUNCH_L(Q, LOSS_MSE);                                                                      \
+  } while (0)
   switch (qstrips(H)) {
   case 1: LBF_HEAD_LAUNCH(1); break;
   case 2: LBF_HEAD_LAUNCH(2); break;
@@ -462,6 +506,7 @@ void head_fused(hipStream_t s, const float *A, int H, const float *P, int Out, c
   default: LBF_HEAD_LAUNCH(5); break;
   }
 #undef LBF_HEAD_LAUNCH
+#undef LBF_HEAD_LAUNCH_L
   LBF_KERNEL_CHECK();
 }
 

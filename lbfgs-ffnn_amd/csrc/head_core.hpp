@@ -211,7 +211,10 @@ struct HRange {
 // FOLD: accumulate the fold (TileArgs::xr / nfold) into fa; needs H <= 128 (one pass of column strips).
 // TBR: samples the tile holds (64, or 32 for a 32-row GEMM tile: the products over samples then run half
 // their steps; rows >= TBR of As / Dz / ys / xr are neither read nor needed).
-template <bool EXTRA_WAVES, int QM, bool FOLD, int TBR = TB> // EXTRA_WAVES: waves >= 4 only join barriers
+// LOSS: LOSS_MSE as above, or LOSS_XENT (linear output layer, Out >= 2): Z are the logits, the row maximum,
+// the exp-sum and Ysum are reductions over the 16 lanes li of a row group (one DPP row: wave.hpp row16_*,
+// the same bits on every lane), the partial is 2 sum y (lse - z) in fp64 and dZ = (p Ysum - y) inv_scale.
+template <bool EXTRA_WAVES, int QM, bool FOLD, int TBR = TB, int LOSS = LOSS_MSE> // EXTRA_WAVES: waves >= 4 only join barriers
 __device__ inline void tile(const Smem &s, const TileArgs &a, long long b0, int rows, f32x4 (&cw)[QM], double &sse,
                             FoldAcc &fa, const HRange &hr = HRange()) {
   static_assert(TBR == 64 || TBR == 32, "head tile of 64 or 32 samples");
@@ -259,21 +262,51 @@ __device__ inline void tile(const Smem &s, const TileArgs &a, long long b0, int 
         else yv[r] = a.Y[(a.idx ? (long long)a.idx[b0 + row] : b0 + row) * a.Out + li];
       }
     }
-    with_act(a.act_out, [&](auto AC) __attribute__((always_inline)) {
-      constexpr int A = decltype(AC)::value;
+    if constexpr (LOSS == LOSS_XENT) {
+      // Lanes li >= Out enter the maximum as -inf and the sums as 0 (yv is 0 there and on rows >= rows); a
+      // row >= rows holds finite logits (zero activations: the bias), so nothing below is NaN before the mask.
+      const bool lv = li < a.Out;
+      const float bl = s.bias[li];
+      float z[4], m[4], e[4], se[4], ysum[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        z[r] = acc[r] + bl;
+        m[r] = row16_max_f32(lv ? z[r] : -INFINITY);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        e[r] = lv ? expf(z[r] - m[r]) : 0.0f;
+        se[r] = row16_sum_f32(e[r]);
+        ysum[r] = row16_sum_f32(yv[r]);
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = r0 + g * 4 + r;
         float dz = 0.0f;
-        if (row < rows && li < a.Out) {
-          const float av = act_c<A>(acc[r] + s.bias[li]);
-          const float d = av - yv[r];
-          sse += double(d) * double(d);
-          dz = d * dact_c<A>(av) * a.sc;
+        if (row < rows && lv) {
+          const float lz = (m[r] - z[r]) + logf(se[r]); // lse - z >= 0
+          sse += 2.0 * double(yv[r]) * double(lz);
+          dz = (e[r] * (1.0f / se[r]) * ysum[r] - yv[r]) * a.sc;
         }
         s.Dz[row * LDZ + dzc] = dz;
       }
-    });
+    } else {
+      with_act(a.act_out, [&](auto AC) __attribute__((always_inline)) {
+        constexpr int A = decltype(AC)::value;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = r0 + g * 4 + r;
+          float dz = 0.0f;
+          if (row < rows && li < a.Out) {
+            const float av = act_c<A>(acc[r] + s.bias[li]);
+            const float d = av - yv[r];
+            sse += double(d) * double(d);
+            dz = d * dact_c<A>(av) * a.sc;
+          }
+          s.Dz[row * LDZ + dzc] = dz;
+        }
+      });
+    }
   }
   lds_barrier();
   KT(36);

@@ -25,7 +25,14 @@ enum Act : int { ACT_LINEAR = 0, ACT_TANH = 1, ACT_RELU = 2, ACT_SIGMOID = 3 };
 // shard); TILE_64x64 (split-K weight gradients with fewer, longer splits); TILE_64x128 (mid-size
 // shards: two workgroups per CU where 128-row tiles would leave one).
 enum GemmTile : int { TILE_AUTO = 0, TILE_32x128 = 1, TILE_64x64 = 2, TILE_64x128 = 3 };
-enum GemmEpi : int { EPI_FWD = 0, EPI_DX = 1, EPI_STORE = 2, EPI_HEAD = 3 };
+// EPI_HEAD_XENT: EPI_HEAD with the softmax cross-entropy loss (gemm() picks it from GemmDesc::head_loss; a
+// compile-time constant of its own, so the squared-error instantiations are the code they were).
+enum GemmEpi : int { EPI_FWD = 0, EPI_DX = 1, EPI_STORE = 2, EPI_HEAD = 3, EPI_HEAD_XENT = 4 };
+constexpr bool epi_head(int epi) { return epi == EPI_HEAD || epi == EPI_HEAD_XENT; }
+// Loss of the output layer (LBF_LOSS_* of the C ABI). LOSS_XENT: softmax cross-entropy on the logits of a
+// linear last layer, loss = inv_scale sum_b sum_o y (lse - z), dZ = inv_scale (p Ysum - y). Every head writes
+// S = 2 sum y (lse - z) as its partial, so 0.5 S inv_scale above the head is the loss, as for the SSE.
+enum Loss : int { LOSS_MSE = 0, LOSS_XENT = 1 };
 
 struct EarlyLs;
 
@@ -72,6 +79,7 @@ struct GemmDesc {
   // output layer on each 64-row half in LDS (head_core.hpp) instead of storing the activations.
   const float *head_P = nullptr; // [W ; b] of the output layer
   int head_out = 0, head_act = ACT_LINEAR;
+  int head_loss = LOSS_MSE;
   const float *head_Y = nullptr;
   const int *head_idx = nullptr; // minibatch rows of Y (nullable)
   double head_inv_scale = 1.0;
@@ -112,6 +120,10 @@ int fold_rows(hipStream_t s, const double *P, int nrows, int ncols, int groups, 
 int loss_partials_wg(long long B, int Out);
 void loss_diff(hipStream_t s, const float *Aout, long long lda, const float *Y, long long ldy, const int *idx,
                long long B, int Out, int act, double inv_scale, float *dZ, long long ldz, double *partials);
+// The same for LOSS_XENT, row-wise (one wave per row, lanes strided over Out): Z holds the logits;
+// dZ = (softmax(Z) Ysum - y) * inv_scale ; per-WG partial of 2 sum y (lse - z). Same grid and partial layout.
+void loss_xent(hipStream_t s, const float *Z, long long ldz_in, const float *Y, long long ldy, const int *idx,
+               long long B, int Out, double inv_scale, float *dZ, long long ldz, double *partials);
 
 // Fused output layer (head.hip): forward + MSE + dZ + delta_prev + per-tile [dW ; db] slabs.
 bool head_supported(int H, int Out);
@@ -119,7 +131,7 @@ int head_tile(int H);
 int head_nwg(long long B, int H);
 void head_fused(hipStream_t s, const float *A, int H, const float *P, int Out, const float *Y, const int *idx,
                 long long B, int act_out, int act_prev, double inv_scale, float *delta, float *slab,
-                double *sse_part, const int *abort = nullptr);
+                double *sse_part, const int *abort = nullptr, int loss = LOSS_MSE);
 
 // The same output layer fed straight from the last hidden layer's forward split-K slabs (small batches,
 // e.g. S-LBFGS's 256-row minibatches on 784-512-256-10): one wave per sample row finishes the row's
@@ -142,6 +154,7 @@ struct RowHeadArgs {
   float *delta = nullptr, *slab = nullptr;
   double *sse_part = nullptr;
   const int *abort = nullptr;
+  int loss = LOSS_MSE;
 };
 bool rowhead_supported(int H, int Out);
 int rowhead_rpw(long long B);
@@ -206,6 +219,9 @@ void reduce_all(hipStream_t s, const RedAllArgs &a);
 void rop_act(hipStream_t s, long long n, const float *A, const float *RZ, int act, float *RA);
 void rop_out(hipStream_t s, long long B, int Out, const float *A, const float *Y, const int *idx, const float *RZ,
              int act, double inv_scale, float *RdZ);
+// LOSS_XENT: RdZ = s Ysum p .* (RZ - sum_k p_k RZ_k) per row, p = softmax(Z) (one wave per row)
+void rop_out_xent(hipStream_t s, long long B, int Out, const float *Z, const float *Y, const int *idx,
+                  const float *RZ, double inv_scale, float *RdZ);
 void rop_back(hipStream_t s, long long n, const float *T1, const float *T2, const float *delta, const float *A,
               const float *RZ, int act, float *out);
 bool act_has_d2(int act);

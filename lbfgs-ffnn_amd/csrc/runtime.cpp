@@ -392,6 +392,27 @@ const float *Mlp::forward(const float *P, const float *X, const int *idx, long l
   return in;
 }
 
+void Mlp::set_loss(int loss) {
+  LBF_REQUIRE(loss == LOSS_MSE || loss == LOSS_XENT, "unknown loss");
+  if (loss == LOSS_XENT) {
+    const Layer &Lo = layers_.back();
+    LBF_REQUIRE(Lo.act == ACT_LINEAR, "softmax cross-entropy needs a linear last layer (the logits)");
+    LBF_REQUIRE(Lo.out >= 2, "softmax cross-entropy needs at least two outputs");
+  }
+  loss_ = loss;
+}
+
+void Mlp::out_loss(const float *Y, const int *idx, long long B, double inv_scale) {
+  const size_t nl = layers_.size();
+  const Layer &Lo = layers_[nl - 1];
+  if (loss_ == LOSS_XENT)
+    loss_xent(ctx_->stream, A_[nl - 1].get(), Lo.out, Y, Lo.out, idx, B, Lo.out, inv_scale, D_[nl - 1].get(), Lo.out,
+              loss_part_.get());
+  else
+    loss_diff(ctx_->stream, A_[nl - 1].get(), Lo.out, Y, Lo.out, idx, B, Lo.out, Lo.act, inv_scale, D_[nl - 1].get(),
+              Lo.out, loss_part_.get());
+}
+
 // Forward phase of an evaluation: every forward GEMM, the output layer (fused head or loss_diff) with
 // its SSE partials, delta of the last layer the head covers, and the head's [dW ; db] partial slabs.
 // What the backward phase needs is kept in fs_.
@@ -435,6 +456,7 @@ void Mlp::forward_phase(const float *P, const float *X, const float *Y, const in
     r.slab = head_slab_.get();
     r.sse_part = loss_part_.get();
     r.abort = ctx_->abort;
+    r.loss = loss_;
     nloss = rowhead_nwg(B);
     {
       ProfScope ps(ctx_, PK_LOSS);
@@ -449,6 +471,7 @@ void Mlp::forward_phase(const float *P, const float *X, const float *Y, const in
     d.head_P = P + Lo.off;
     d.head_out = Lo.out;
     d.head_act = Lo.act;
+    d.head_loss = loss_;
     d.head_Y = Y;
     d.head_idx = idx;
     d.head_inv_scale = inv_scale;
@@ -466,14 +489,13 @@ void Mlp::forward_phase(const float *P, const float *X, const float *Y, const in
     {
       ProfScope ps(ctx_, PK_LOSS);
       head_fused(s, A_[nl - 2].get(), Lo.in, P + Lo.off, Lo.out, Y, idx, B, Lo.act, layers_[nl - 2].act, inv_scale,
-                 D_[nl - 2].get(), head_slab_.get(), loss_part_.get(), ctx_->abort);
+                 D_[nl - 2].get(), head_slab_.get(), loss_part_.get(), ctx_->abort, loss_);
     }
     lstart = nl - 2;
   } else {
     nloss = loss_partials_wg(std::max(1LL, B), Lo.out);
     ProfScope ps(ctx_, PK_LOSS);
-    loss_diff(s, A_[nl - 1].get(), Lo.out, Y, Lo.out, idx, B, Lo.out, Lo.act, inv_scale, D_[nl - 1].get(), Lo.out,
-              loss_part_.get());
+    out_loss(Y, idx, B, inv_scale);
     lstart = nl - 1;
   }
   fs_.B = B;
@@ -828,15 +850,13 @@ void Mlp::batch_grads(const float *P, const float *X, const float *Y, int nmb, l
   LBF_REQUIRE(ldg >= (long long)nparams_, "batch_grads: gradient stride below the parameter count");
   hipStream_t s = ctx_->stream;
   const int nl = int(layers_.size());
-  const Layer &Lo = layers_[nl - 1];
   const long long R = (long long)nmb * cnt;
   ensure(R);
   // forward over every row (no fused head: its [dW ; db] partials are per 64-row tile, not per minibatch)
   forward(P, X, nullptr, R, nl);
   {
     ProfScope ps(ctx_, PK_LOSS);
-    loss_diff(s, A_[nl - 1].get(), Lo.out, Y, Lo.out, nullptr, R, Lo.out, Lo.act, inv_scale, D_[nl - 1].get(),
-              Lo.out, loss_part_.get());
+    out_loss(Y, nullptr, R, inv_scale);
   }
   for (int l = nl - 1; l >= 0; --l) {
     const Layer &L = layers_[l];
@@ -1026,8 +1046,7 @@ void Mlp::hvp(const float *P, const float *V, const float *X, const float *Y, co
   // ---- forward and the plain backward (dZ_l; delta_l where act'' != 0) ----
   forward(P, X, idx, B, nl);
   const Layer &Lo = layers_[size_t(nl - 1)];
-  loss_diff(s, A_[size_t(nl - 1)].get(), Lo.out, Y, Lo.out, idx, B, Lo.out, Lo.act, inv_scale,
-            D_[size_t(nl - 1)].get(), Lo.out, loss_part_.get());
+  out_loss(Y, idx, B, inv_scale);
   for (int l = nl - 1; l >= 1; --l) {
     const int pa = layers_[size_t(l - 1)].act;
     back_prod(l, D_[size_t(l)].get(), P, pa, D_[size_t(l - 1)].get());
@@ -1047,8 +1066,12 @@ void Mlp::hvp(const float *P, const float *V, const float *X, const float *Y, co
     rop_act(s, nz, A_[size_t(l)].get(), RZ_[size_t(l)].get(), L.act, RA_[size_t(l)].get());
   }
   // ---- R-backward ----
-  rop_out(s, B, Lo.out, A_[size_t(nl - 1)].get(), Y, idx, RZ_[size_t(nl - 1)].get(), Lo.act, inv_scale,
-          RD_[size_t(nl - 1)].get());
+  if (loss_ == LOSS_XENT)
+    rop_out_xent(s, B, Lo.out, A_[size_t(nl - 1)].get(), Y, idx, RZ_[size_t(nl - 1)].get(), inv_scale,
+                 RD_[size_t(nl - 1)].get());
+  else
+    rop_out(s, B, Lo.out, A_[size_t(nl - 1)].get(), Y, idx, RZ_[size_t(nl - 1)].get(), Lo.act, inv_scale,
+            RD_[size_t(nl - 1)].get());
   for (int l = nl - 1; l >= 0; --l) {
     const Layer &L = layers_[size_t(l)];
     float *dst = Hv + L.off;

@@ -117,6 +117,10 @@ public:
   size_t nparams() const { return nparams_; }
   const std::vector<Layer> &layers() const { return layers_; }
   Ctx *ctx() const { return ctx_; }
+  // The loss every evaluation below minimises (kernels.hpp Loss); LOSS_XENT needs a linear last layer with
+  // at least two outputs. Takes effect from the next evaluation; the workspace and the plan do not depend on it.
+  void set_loss(int loss);
+  int loss() const { return loss_; }
 
   // Forward only: activations of every layer into the workspace; returns the output buffer.
   // raw_last: the last layer run stays as its split-K slabs in fslab_buf(l) (no fwd_reduce_act; rowhead reads them)
@@ -198,6 +202,9 @@ private:
   Ctx *ctx_;
   std::vector<Layer> layers_;
   size_t nparams_ = 0;
+  int loss_ = LOSS_MSE;
+  // the output layer on the generic route: loss_diff or loss_xent on A_[nl - 1] -> D_[nl - 1], loss_part_
+  void out_loss(const float *Y, const int *idx, long long B, double inv_scale);
   long long cap_ = -1, planned_ = -1;
   std::vector<DevBuf<float>> A_, D_;
   DevBuf<float> slab_, head_slab_, fslab_, fslab2_;

@@ -651,6 +651,7 @@ SlbfgsSolver::SlbfgsSolver(Mlp *net, const lbf_slbfgs_params &prm, float *d_para
     }
     dims.push_back(net->layers().back().out);
     tnet_.reset(new Mlp(tctx_.get(), int(acts.size()), dims.data(), acts.data()));
+    tnet_->set_loss(net->loss()); // the twins evaluate the caller's objective
     LBF_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming | event_release_flags()));
     LBF_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming | event_release_flags()));
     for (int i = 0; i < 2; ++i) {
@@ -671,6 +672,7 @@ SlbfgsSolver::SlbfgsSolver(Mlp *net, const lbf_slbfgs_params &prm, float *d_para
       fctx_->prof.only = ctx_->prof.only;
       fctx_->prof.every = ctx_->prof.every;
       fnet_.reset(new Mlp(fctx_.get(), int(acts.size()), dims.data(), acts.data()));
+      fnet_->set_loss(net->loss());
       mu_next_.resize(ng);
       fscal_.resize(SC_N);
       LBF_HIP(hipMemsetAsync(fscal_.get(), 0, SC_N * sizeof(double), ctx_->stream));

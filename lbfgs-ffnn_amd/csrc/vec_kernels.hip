@@ -141,6 +141,47 @@ void loss_diff(hipStream_t s, const float *Aout, long long lda, const float *Y, 
   LBF_KERNEL_CHECK();
 }
 
+// Softmax cross-entropy on the logits Z (LOSS_XENT), row-wise: wave w of block k takes rows 4k + w,
+// 4k + w + 4 gridDim, ...; its lanes stride over the Out logits in three passes (maximum; exp-sum, Ysum;
+// loss terms and dZ: the row is a few cache lines, re-read from L1/L2). lse - z_o = (m - z_o) + log(se).
+// Partial per block: 2 sum y (lse - z), fp64, fixed order (lane accumulators, block_sum).
+__global__ __launch_bounds__(256) void loss_xent_kernel(const float *Z, long long ldz_in, const float *Y, long long ldy,
+                                                        const int *idx, long long B, int Out, double inv_scale,
+                                                        float *dZ, long long ldz, double *partials) {
+  __shared__ double scratch[16];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float sc = float(inv_scale);
+  double acc[1] = {0.0};
+  for (long long b = (long long)blockIdx.x * 4 + wave; b < B; b += (long long)gridDim.x * 4) { // wave-uniform
+    const float *z = Z + b * ldz_in;
+    const float *y = Y + (idx ? (long long)idx[b] : b) * ldy;
+    float m = -INFINITY;
+    for (int o = lane; o < Out; o += 64) m = fmaxf(m, z[o]);
+    m = wave_max_f32(m);
+    double se = 0.0, ys = 0.0;
+    for (int o = lane; o < Out; o += 64) {
+      se += double(expf(z[o] - m));
+      ys += double(y[o]);
+    }
+    const float sef = float(wave_sum(se)), ysum = float(wave_sum(ys));
+    const float lg = logf(sef), rs = 1.0f / sef;
+    for (int o = lane; o < Out; o += 64) {
+      const float zo = z[o], yo = y[o];
+      acc[0] += 2.0 * double(yo) * double((m - zo) + lg);
+      dZ[b * ldz + o] = (expf(zo - m) * rs * ysum - yo) * sc;
+    }
+  }
+  block_sum<1>(acc, scratch);
+  if (threadIdx.x == 0) partials[blockIdx.x] = acc[0];
+}
+
+void loss_xent(hipStream_t s, const float *Z, long long ldz_in, const float *Y, long long ldy, const int *idx,
+               long long B, int Out, double inv_scale, float *dZ, long long ldz, double *partials) {
+  hipLaunchKernelGGL(loss_xent_kernel, dim3(loss_partials_wg(B, Out)), dim3(256), 0, s, Z, ldz_in, Y, ldy, idx, B,
+                     Out, inv_scale, dZ, ldz, partials);
+  LBF_KERNEL_CHECK();
+}
+
 // ---------------------------------------------------------------------------------------------
 // split-K slab reduction -> flat gradient segment
 // ---------------------------------------------------------------------------------------------

@@ -34,6 +34,34 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return lane_f64(v, 63);
 }
 
+// Reductions over a DPP row (the 16 lanes l & ~15 .. l | 15): quad_perm [1,0,3,2] and [2,3,0,1], then
+// row_half_mirror and row_mirror. Each step combines a lane's value with its partner's, and both partners
+// form the same commutative pair, so all 16 lanes end with the same bits. Used by the softmax head, where
+// lane (li, g) holds output li of a sample and a row group g is one DPP row.
+template <int CTRL> __device__ __forceinline__ float dpp_row_f32(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
+}
+__device__ __forceinline__ float row16_max_f32(float v) {
+  v = fmaxf(v, dpp_row_f32<0xB1>(v));
+  v = fmaxf(v, dpp_row_f32<0x4E>(v));
+  v = fmaxf(v, dpp_row_f32<0x141>(v));
+  v = fmaxf(v, dpp_row_f32<0x140>(v));
+  return v;
+}
+__device__ __forceinline__ float row16_sum_f32(float v) {
+  v += dpp_row_f32<0xB1>(v);
+  v += dpp_row_f32<0x4E>(v);
+  v += dpp_row_f32<0x141>(v);
+  v += dpp_row_f32<0x140>(v);
+  return v;
+}
+// Wave-wide maximum, the same bits on every lane (butterfly: each step pairs a lane with its partner).
+__device__ __forceinline__ float wave_max_f32(float v) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+
 // Workgroup barrier that orders LDS only. __syncthreads() carries a workgroup-scope release, which on
 // gfx950 means s_waitcnt vmcnt(0): every global store the wave has in flight must be acknowledged
 // (~1 us) before the barrier. Where no thread reads, after the barrier, global memory written before

@@ -13,8 +13,8 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import (ACTS, INIT_CPU, INIT_CUDA, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED, SLBFGS_DP_SLICED, GdParams,
-                   LbfError, LbfgsParams, Record, SgdParams, SlbfgsParams, SolveInfo, check, lib, ptr)
+from ._lib import (ACTS, INIT_CPU, INIT_CUDA, LOSSES, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED, SLBFGS_DP_SLICED,
+                   GdParams, LbfError, LbfgsParams, Record, SgdParams, SlbfgsParams, SolveInfo, check, lib, ptr)
 
 
 class Context:
@@ -145,7 +145,11 @@ class Context:
 class Mlp:
     """Dense MLP; flat fp32 params in the reference layout [W (Out x In col-major) | b] per layer."""
 
-    def __init__(self, ctx: Context, dims: Sequence[int], acts: Sequence):
+    def __init__(self, ctx: Context, dims: Sequence[int], acts: Sequence, loss: str = "mse"):
+        """loss: "mse" (0.5 inv_scale ||net(X) - Y||^2, the reference's) or "softmax_xent" (softmax
+        cross-entropy on the logits of a linear last layer; lbf_mlp_set_loss)."""
+        if loss not in LOSSES:  # before anything touches the device
+            raise LbfError(f"unknown loss {loss!r}: expected one of {sorted(LOSSES)}")
         self.ctx = ctx
         self.dims = [int(d) for d in dims]
         self.acts = [ACTS[a] if isinstance(a, str) else int(a) for a in acts]
@@ -156,6 +160,21 @@ class Mlp:
         check(lib().lbf_mlp_create(ctx.h, len(self.acts), d, a, C.byref(h)), "lbf_mlp_create")
         self.h = h
         self.nparams = int(lib().lbf_mlp_param_count(h))
+        if loss != "mse":
+            self.loss_name = loss
+
+    @property
+    def loss_name(self) -> str:
+        """The loss every evaluation and solver on this network minimises ("mse" or "softmax_xent")."""
+        v = C.c_int(-1)
+        check(lib().lbf_mlp_get_loss(self.h, C.byref(v)), "lbf_mlp_get_loss")
+        return next(k for k, c in LOSSES.items() if c == v.value)
+
+    @loss_name.setter
+    def loss_name(self, loss: str):
+        if loss not in LOSSES:
+            raise LbfError(f"unknown loss {loss!r}: expected one of {sorted(LOSSES)}")
+        check(lib().lbf_mlp_set_loss(self.h, LOSSES[loss]), "lbf_mlp_set_loss")
 
     def _check_data(self, X: torch.Tensor, Y: Optional[torch.Tensor]):
         """X [rows][In], Y [rows][Out] (the reference's column-major In x N / Out x N)."""
@@ -319,6 +338,42 @@ def lbfgs_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor
     n_local = int(X.shape[0])
     check(lib().lbf_lbfgs_solve(net.h, C.byref(p), ptr(params), ptr(X), ptr(Y), n_local,
                                 int(n_global or n_local), C.byref(hist.rec), C.byref(info)), "lbf_lbfgs_solve")
+    return hist.as_dict(), info
+
+
+_LOSS_GRAD_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_void_p, C.c_void_p)  # lbf_loss_grad_fn
+
+
+def lbfgs_solve_fn(ctx: Context, params: torch.Tensor, fn, line_search: str = "wolfe", **kw):
+    """L-BFGS on an arbitrary objective (lbf_lbfgs_solve_fn): ``loss = fn(p, g)`` is called once per trial with
+    the trial point ``p`` (a device tensor, read-only) and must write the gradient into the device tensor ``g``
+    and return the loss. params updated in place. Returns (history dict, SolveInfo). The engine hands the
+    callback raw device pointers; they are copied to and from the two tensors (device to device)."""
+    p = lbfgs_params(line_search, **kw)
+    hist = History(p.max_iters)
+    info = SolveInfo()
+    n = int(params.numel())
+    pt, gt = torch.empty_like(params), torch.empty_like(params)
+    nbytes = 4 * n
+    failed = []
+
+    def trampoline(_user, d_params, d_grad):
+        try:
+            check(lib().lbf_memcpy(ctx.h, ptr(pt), C.c_void_p(d_params), nbytes, 2), "lbf_memcpy")
+            loss = float(fn(pt, gt))
+            torch.cuda.synchronize(ctx.device)
+            check(lib().lbf_memcpy(ctx.h, C.c_void_p(d_grad), ptr(gt), nbytes, 2), "lbf_memcpy")
+            return loss
+        except BaseException as e:  # an exception cannot cross the C frames: reported after the solve returns
+            failed.append(e)
+            return float("nan")
+
+    cb = _LOSS_GRAD_FN(trampoline)
+    rc = lib().lbf_lbfgs_solve_fn(ctx.h, C.byref(p), n, ptr(params, numel=n), C.cast(cb, C.c_void_p), None,
+                                  C.byref(hist.rec), C.byref(info))
+    if failed:
+        raise failed[0]
+    check(rc, "lbf_lbfgs_solve_fn")
     return hist.as_dict(), info
 
 

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import engine
-from ._lib import LbfError
+from ._lib import LOSSES, LbfError
 
 
 @dataclass
@@ -46,6 +46,8 @@ class UnifiedConfig:
     line_search: str = "wolfe"   # "wolfe" = CPU semantics (parity target), "armijo" = CUDA semantics
     init: str = "cpu"            # "cpu" (network.hpp:45-71) or "cuda" (network.cuh:36-59) init stream
     write_csv: bool = True
+    loss: str = "mse"            # "mse" or "softmax_xent" (HIP extension; train() applies a non-default choice
+                                 # like UnifiedLauncher.setLoss, and it then stays the network's loss)
 
 
 @dataclass
@@ -106,6 +108,14 @@ class _DeviceNet:
         self.layers = []
         self.mlp: Optional[engine.Mlp] = None
         self.params: Optional[torch.Tensor] = None
+        self.loss = "mse"
+
+    def setLoss(self, loss: str):
+        if loss not in LOSSES:
+            raise LbfError(f"unknown loss {loss!r}: expected one of {sorted(LOSSES)}")
+        if self.mlp is not None:
+            self.mlp.loss_name = loss
+        self.loss = loss
 
     def addLayer(self, In: int, Out: int, act):
         if self.layers and self.layers[-1][1] != In:
@@ -115,7 +125,7 @@ class _DeviceNet:
     def bindParams(self, seed: int = 123, mode: str = "cpu"):
         dims = [self.layers[0][0]] + [l[1] for l in self.layers]
         if self.mlp is None:
-            self.mlp = engine.Mlp(self.ctx, dims, [l[2] for l in self.layers])
+            self.mlp = engine.Mlp(self.ctx, dims, [l[2] for l in self.layers], loss=self.loss)
             self.params = self.mlp.new_params()
         self.mlp.init_params(seed, mode, self.params)
 
@@ -241,6 +251,11 @@ class UnifiedLauncher:
     def buildNetwork(self):
         self.net_wrapper_.bindParams()
 
+    def setLoss(self, loss: str):
+        """The loss the optimizers minimise and evaluate() reports: "mse" (default) or "softmax_xent" (softmax
+        cross-entropy on the logits; the last layer must be linear). Before or after buildNetwork()."""
+        self.net_wrapper_.setLoss(loss)
+
     def setData(self, data: UnifiedDataset):
         self.dataset_ = data
         self.data_ = _DeviceData(data, f"cuda:{self.ctx.device}", self.rank, self.world)
@@ -248,6 +263,8 @@ class UnifiedLauncher:
     def train(self, optimizer: UnifiedOptimizer, config: UnifiedConfig):
         if self.rank == 0:
             print(f">>> Running HIP Experiment: {config.name}")
+        if config.loss != "mse":
+            self.setLoss(config.loss)
         if config.reset_params:
             self.net_wrapper_.bindParams(config.seed, config.init)
         recorder = optimizer.optimize(self.net_wrapper_, self.data_, config)
@@ -263,9 +280,16 @@ class UnifiedLauncher:
         return self.evaluate(self.data_.test_x, self.data_.test_y, "Test Results")
 
     def evaluate(self, x: torch.Tensor, y: np.ndarray, label: str):
-        """unified_launcher.hpp:154-199: forward on the device, accuracy + mean MSE on the host."""
+        """unified_launcher.hpp:154-199: forward on the device, accuracy + mean MSE on the host. With the
+        cross-entropy loss the outputs are logits and the mean cross-entropy per sample is reported in the MSE's
+        place (same label and key); the argmax is the same."""
         out = self.net_wrapper_.mlp.forward(self.net_wrapper_.params, x).double().cpu().numpy()
-        mse = float(((out - y) ** 2).mean()) if out.size else 0.0
+        if self.net_wrapper_.loss == "softmax_xent" and out.size:
+            m = out.max(1, keepdims=True)
+            lse = m + np.log(np.exp(out - m).sum(1, keepdims=True))
+            mse = float((y * (lse - out)).sum(1).mean())
+        else:
+            mse = float(((out - y) ** 2).mean()) if out.size else 0.0
         acc = float((out.argmax(1) == y.argmax(1)).mean() * 100.0) if out.size else 0.0
         if self.rank == 0:
             print(f"{label}: MSE={mse:g}, Accuracy={acc:g}%")
