@@ -149,6 +149,19 @@ int lbf_mlp_fd_hvp(lbf_mlp *net, const float *d_params, const float *d_v, const 
 #define LBF_LOSS_SOFTMAX_XENT 1
 int lbf_mlp_set_loss(lbf_mlp *net, int loss);
 int lbf_mlp_get_loss(const lbf_mlp *net, int *loss);
+/* L2 weight decay of the solvers that take no lambda of their own (extension; the reference's full-batch
+ * solvers have none). lbf_lbfgs_solve, lbf_lbfgs_begin / iterate / end, lbf_gd_solve and lbf_sgd_solve on the
+ * network minimise
+ *   data loss + 0.5*l2*||w||^2
+ * with either loss, and everything they report includes the penalty: lbf_record.loss and grad_norm, the line
+ * search's f, final_loss and final_grad_norm (gradient: data gradient + l2*w). SGD's epoch loss is then the
+ * row-weighted mean of the batch objectives, penalty included. Default 0; l2 < 0 or a non-finite value returns
+ * LBF_ERR_INVALID. A property of the network, like the loss: read at *_begin / at the start of a solve, and it
+ * must not be changed between *_begin and *_end. NOT affected: the functions with an l2 argument of their own
+ * (lbf_mlp_loss_grad, lbf_mlp_hvp, lbf_mlp_fd_hvp, lbf_mlp_batch_grads), lbf_slbfgs_* (lbf_slbfgs_params.lambda),
+ * lbf_mlp_loss (the data term) and lbf_lbfgs_solve_fn (the callback is the whole objective). */
+int lbf_mlp_set_l2(lbf_mlp *net, double l2);
+int lbf_mlp_get_l2(const lbf_mlp *net, double *l2);
 int lbf_two_loop(lbf_ctx *ctx, long long n, int k, const float *d_S, const float *d_Y, const double *h_rho,
                  const float *d_g, float *d_dir, int mode);
 

@@ -146,6 +146,7 @@ public:
       params_.resize(size_t(lbf_mlp_param_count(net_)));
       grads_.resize(params_.size());
       if (loss_ != Loss::MeanSquaredError) hip_check(lbf_mlp_set_loss(net_, int(loss_)), "lbf_mlp_set_loss");
+      if (l2_ != 0.0) hip_check(lbf_mlp_set_l2(net_, l2_), "lbf_mlp_set_l2");
     }
     hip_check(lbf_mlp_init_params(net_, seed, init_mode, params_.data()), "lbf_mlp_init_params");
   }
@@ -156,6 +157,16 @@ public:
     loss_ = loss;
   }
   Loss loss() const { return loss_; }
+  /// L2 weight decay of the full-batch L-BFGS, GD and SGD solvers on this network (lbf_mlp_set_l2): they minimise
+  /// data loss + 0.5 l2 |w|^2 and report it. Before or after bindParams(); not between a stateful solver's begin
+  /// and end. compute_loss_and_grad, forward_only and the launcher's evaluate() keep the data term only. A
+  /// negative or non-finite value aborts like any engine error.
+  void setL2(double l2) {
+    if (net_) hip_check(lbf_mlp_set_l2(net_, l2), "lbf_mlp_set_l2");
+    else if (!(l2 >= 0.0) || l2 > 1.7976931348623157e308) hip_check(LBF_ERR_INVALID, "lbf_mlp_set_l2");
+    l2_ = l2;
+  }
+  double l2() const { return l2_; }
   size_t params_size() const { return params_.size(); }
   int output_size() const { return dims_.empty() ? 0 : dims_.back(); }
   HipScalar *params_data() { return params_.data(); }
@@ -180,6 +191,7 @@ private:
   lbf_mlp *net_ = nullptr;
   std::vector<int> dims_, acts_;
   Loss loss_ = Loss::MeanSquaredError;
+  double l2_ = 0.0;
   DeviceBuffer<HipScalar> params_, grads_;
 };
 
@@ -374,6 +386,7 @@ struct UnifiedConfig {
   int log_interval = 10;
   bool reset_params = true;
   unsigned int seed = 123u;
+  double l2 = 0.0; ///< HIP extension: train() applies a non-zero value like UnifiedLauncher::setL2
 };
 /// src/unified_optimization.hpp:54-59 (HostMatrix instead of Eigen::MatrixXd)
 struct UnifiedDataset {
@@ -549,6 +562,8 @@ public:
   /// The loss train() minimises and evaluate() reports (default: the reference's MSE). It lives on the network,
   /// not in UnifiedConfig, which in reference mode is the reference's own struct.
   void setLoss(hip_mlp::Loss loss) { net_wrapper_.getInternal().setLoss(loss); }
+  /// L2 weight decay of UnifiedLBFGS / UnifiedGD / UnifiedSGD (HipNetwork::setL2); evaluate() reports the data term.
+  void setL2(double l2) { net_wrapper_.getInternal().setL2(l2); }
 
   /// Host -> device upload with the fp64 -> fp32 conversion of unified_launcher.hpp:105-128; like the reference
   /// it keeps a copy of the dataset, which train() hands to the strategy as host_data.
@@ -566,6 +581,9 @@ public:
 
   void train(UnifiedOptimizer<HipBackend> &optimizer, const UnifiedConfig &config) {
     std::cout << ">>> Running HIP Experiment: " << config.name << std::endl;
+#ifndef LBF_USE_REFERENCE_UNIFIED_TYPES
+    if (config.l2 != 0.0) setL2(config.l2);
+#endif
     if (config.reset_params) net_wrapper_.bindParams(config.seed);
     optimizer.optimize(handle_, net_wrapper_, dataset_, d_train_x_, d_train_y_, config);
     last_train_ = evaluate(train_y_, d_train_x_, n_train_, "Training Results");

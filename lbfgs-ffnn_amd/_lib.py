@@ -143,6 +143,8 @@ def lib():
         "lbf_synth_regression": (C.c_int, [_vp, C.c_longlong, C.c_longlong, C.c_int, C.c_uint, C.c_uint, _vp, _vp]),
         "lbf_mlp_set_loss": (C.c_int, [_vp, C.c_int]),
         "lbf_mlp_get_loss": (C.c_int, [_vp, _ip]),
+        "lbf_mlp_set_l2": (C.c_int, [_vp, C.c_double]),
+        "lbf_mlp_get_l2": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -161,7 +163,18 @@ EXPORTS = ("lbf_last_error lbf_version lbf_abi_version lbf_ctx_create lbf_ctx_de
            "lbf_lbfgs_begin lbf_lbfgs_iterate lbf_lbfgs_end lbf_lbfgs_solve_fn lbf_device_alloc lbf_device_free lbf_memcpy lbf_slbfgs_solve lbf_slbfgs_begin lbf_slbfgs_iterate lbf_slbfgs_end lbf_slbfgs_pair0 lbf_slbfgs_pair_io lbf_prof_enable lbf_prof_select lbf_prof_sample lbf_prof_read lbf_prof_read_work lbf_synth_mnist "
            "lbf_sample_indices lbf_synth_regression lbf_gd_default_params lbf_sgd_default_params lbf_gd_solve "
            "lbf_sgd_solve lbf_idx_read_images lbf_idx_read_labels lbf_mlp_hvp lbf_mlp_fd_hvp lbf_mlp_loss "
-           "lbf_mlp_set_loss lbf_mlp_get_loss").split()
+           "lbf_mlp_set_loss lbf_mlp_get_loss lbf_mlp_set_l2 lbf_mlp_get_l2").split()
+
+
+def check_l2(l2) -> float:
+    """A weight-decay coefficient: a finite number >= 0 (checked before anything touches the device)."""
+    try:
+        v = float(l2)
+    except (TypeError, ValueError):
+        raise LbfError(f"l2 must be a number, got {l2!r}") from None
+    if not (v >= 0.0) or v == float("inf"):
+        raise LbfError(f"l2 must be finite and >= 0, got {l2!r}")
+    return v
 
 
 def check(rc: int, what: str) -> None:

@@ -297,6 +297,20 @@ int lbf_mlp_get_loss(const lbf_mlp *net, int *loss) {
   });
 }
 
+int lbf_mlp_set_l2(lbf_mlp *net, double l2) {
+  return guard([&] {
+    LBF_REQUIRE(net, "null argument");
+    net->net->set_l2(l2);
+  });
+}
+
+int lbf_mlp_get_l2(const lbf_mlp *net, double *l2) {
+  return guard([&] {
+    LBF_REQUIRE(net && l2, "null argument");
+    *l2 = net->net->l2();
+  });
+}
+
 int lbf_mlp_fd_hvp(lbf_mlp *net, const float *d_params, const float *d_v, const float *d_X, const float *d_Y,
                    const int *d_idx, long long batch, double inv_scale, double l2, double eps, float *d_y) {
   return guard([&] {

@@ -84,6 +84,13 @@ __device__ __forceinline__ bool gemm_early_exit(const GemmK &g, float *lds) {
   double sse = 0.0;
   if (t < 256)
     for (int r = t; r < e.nsse; r += 256) sse += e.sse_part[r];
+  // lambda != 0 (an argument, uniform for the launch, tested at each use): the trial point's w.w partials, summed
+  // as the tail sums them (ww_sum). The lambda = 0 path skips three branches; VGPRs, LDS, scratch and occupancy of
+  // every GEMM instantiation are the parent's, the scalar count rises to 50.
+  if (e.ww_part != nullptr) {
+    const double q = ww_sum_wave(e.ww_part, e.nww, t);
+    if (t < 256 && (t & 63) == 0) red[8 + (t >> 6)] = q;
+  }
   double gfo = 0.0, fold = 0.0, alpha0 = 0.0, accept_prev = 0.0;
   int abf = 0;
   if (t == 0) {
@@ -99,12 +106,14 @@ __device__ __forceinline__ bool gemm_early_exit(const GemmK &g, float *lds) {
   __syncthreads();
   if (t == 0) {
     const double sse_t = ((red[0] + red[1]) + red[2]) + red[3];
-    const double fn = 0.5 * sse_t * e.inv_scale; // tail_fin_body's loss (lambda = 0)
+    double fn = 0.5 * sse_t * e.inv_scale; // tail_fin_body's loss
+    if (e.ww_part != nullptr) fn = ww_loss(fn, e.lambda, ww_sum_fin(red + 8));
     const bool fail = !ls_sufficient_decrease(e.ls, fn, fold, gfo);
     if (fail && !abf && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
       double *sc = e.ls.scal;
       sc[SC_SSE] = sse_t;
       sc[SC_LOSS] = fn;
+      if (e.ww_part != nullptr) sc[SC_WW] = ww_sum_fin(red + 8);
       *e.ls.abort = 1;
       SpecRecord *r = e.ls.rec;
       __hip_atomic_store(&r->loss, fn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -36,6 +36,21 @@ enum Loss : int { LOSS_MSE = 0, LOSS_XENT = 1 };
 
 struct EarlyLs;
 
+// The w.w of an L-BFGS trial point, as fp64 partials written by the kernel that wrote the point (hist_combine,
+// axpy_to, or ww_partials): block b the float x float products of elements [b E, (b + 1) E) summed in fp64 in a
+// fixed order, E = ww_block_elems(n), one word per block, no atomics. Every consumer of the point (sse_loss, the
+// early Armijo test, the fused tail, reduce_all's finish, eval_tail) sums these same words in one order
+// (wave.hpp ww_sum), so a loss-only trial, the early test and the full evaluation of one point add the same
+// 0.5 lambda w.w, bit for bit.
+struct WwPart {
+  const double *part = nullptr;
+  int n = 0;
+};
+long long ww_block_elems(long long n); // 256 up to 2^21 elements, then 256 * 2^k keeping the count <= 8192
+int ww_partials_n(long long n);        // partial count: a function of n only
+// the partials of an existing vector in one launch (the points no fused producer wrote)
+void ww_partials(hipStream_t s, long long n, const float *x, double *part, const int *abort = nullptr);
+
 struct GemmDesc {
   int M = 0, N = 0, K = 0;
   const float *A = nullptr;
@@ -207,6 +222,10 @@ struct RedAllArgs {
   double *scal = nullptr;
   const int *abort = nullptr;
   float *sse_hilo = nullptr;    // data parallel: one extra block packs sum(sse_part[0..nsse)) as fp32 (hi, lo) here
+  // lambda != 0 and the point w came with w.w partials (WwPart): SC_WW and the loss's penalty are taken from
+  // them (ww_sum's order) instead of this evaluation's own w.w sweep
+  const double *ww_part = nullptr;
+  int nww = 0;
 };
 constexpr int RA_COLS = 64;
 constexpr int RA_GPB = 4; // column groups per reduce_all block for single-pass segments
@@ -240,21 +259,25 @@ void dot_partials(hipStream_t s, long long n, const float *x, const float *y, do
 void eval_status(hipStream_t s, const double *sse_d, const float *sse_hilo, double inv_scale, double lambda,
                  double *scal);
 // One-workgroup tail: reduce finalize dots (+ SSE partials unless hilo) and write SC_TGG/TGP/WW/SSE/LOSS.
+// ww (part non-null, lambda != 0): SC_WW and the penalty from the point's w.w partials instead of the dots'.
 void eval_tail(hipStream_t s, const double *dots_part, int nd, const double *sse_part, int nsse, const float *hilo,
-               double inv_scale, double lambda, double *scal, const int *abort = nullptr);
+               double inv_scale, double lambda, double *scal, const int *abort = nullptr, WwPart ww = {});
 // DP: reduce SSE partials into an fp32 (hi, lo) pair (all-reduced together with the gradient).
 // Loss-only status of a forward pass: SC_SSE / SC_LOSS from the SSE partials (reduce_fin's order) or,
 // data parallel, from the all-reduced (hi, lo) pair.
+// ww (part non-null): also SC_WW and SC_LOSS += 0.5 lambda w.w from the trial point's partials (the penalty is
+// never part of the reduced words: w is replicated, it is added once, after the all-reduce).
 void sse_loss(hipStream_t s, const double *sse_part, int nsse, const float *hilo, double inv_scale, double *scal,
-              const int *abort);
+              const int *abort, double lambda = 0.0, WwPart ww = {});
 void sse_pack(hipStream_t s, const double *sse_part, int nsse, float *hilo, const int *abort = nullptr);
 // hilo[0] = float(x), hilo[1] = float(x - hilo[0])
 void pack_hilo(hipStream_t s, const double *x, float *hilo);
 
 void axpy(hipStream_t s, long long n, float alpha, const float *x, float *y);
 void scal(hipStream_t s, long long n, float alpha, float *x);
-// y = x + alpha * p
-void axpy_to(hipStream_t s, long long n, const float *x, float alpha, const float *p, float *y);
+// y = x + alpha * p; ww_part (nullable): also y's w.w partials (WwPart, ww_partials_n(n) words)
+void axpy_to(hipStream_t s, long long n, const float *x, float alpha, const float *p, float *y,
+             double *ww_part = nullptr);
 // GD / SGD momentum step and SGD's device-side epoch-loss accumulator (vec_kernels.hip).
 void momentum_step(hipStream_t s, long long n, float momentum, float lr, const float *lr_dev, const float *g, float *v,
                    float *x);
@@ -342,7 +365,7 @@ struct LsCtlArgs {
 };
 void ls_ctl(hipStream_t s, const LsCtlArgs &a);
 
-// Early Armijo test of a speculative first trial (single rank, lambda = 0; GemmDesc::early): every block of
+// Early Armijo test of a speculative first trial (single rank; GemmDesc::early): every block of
 // the trial's first backward GEMM sums the forward's SSE partials exactly as the fused tail's decision does
 // (tail_fin_body), applies ls_rule.hpp's sufficient-decrease test and, when it fails, exits; block 0 then
 // publishes the rejection (SC_LOSS, SC_SSE, the abort flag, the host record as SPEC_REJECT_EARLY), so the
@@ -353,6 +376,10 @@ struct EarlyLs {
   int nsse = 0;
   double inv_scale = 0.0;
   LsCtlArgs ls;
+  // lambda != 0: the trial point's w.w partials, summed as the tail sums them (ww_sum); fn += 0.5 lambda w.w
+  const double *ww_part = nullptr;
+  int nww = 0;
+  double lambda = 0.0;
 };
 
 struct HistView {
@@ -449,6 +476,7 @@ struct CombineArgs {
   float *x_out = nullptr, *x_out2 = nullptr; // x_out = x_in + alpha*dir ; x_out2 = copy of x_out
   int alpha_from_state = 1;                  // alpha = scal[SC_ALPHA0]
   double alpha = 1.0;
+  double *ww_part = nullptr;                 // x_out's w.w partials (WwPart; needs x_out)
 };
 struct DirArgs {
   GramArgs g;               // operands, policy, has_pair / has_g, reset; g.h carries the abort flag

@@ -2,6 +2,7 @@
 #include "runtime.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -392,6 +393,11 @@ const float *Mlp::forward(const float *P, const float *X, const int *idx, long l
   return in;
 }
 
+void Mlp::set_l2(double l2) {
+  LBF_REQUIRE(std::isfinite(l2) && l2 >= 0.0, "l2 must be finite and >= 0");
+  l2_ = l2;
+}
+
 void Mlp::set_loss(int loss) {
   LBF_REQUIRE(loss == LOSS_MSE || loss == LOSS_XENT, "unknown loss");
   if (loss == LOSS_XENT) {
@@ -508,10 +514,12 @@ void Mlp::forward_phase(const float *P, const float *X, const float *Y, const in
 // Loss only (forward phase + the SSE reduction; the reference's f(x) of a line-search trial,
 // full_batch_minimizer.hpp:136): SC_SSE / SC_LOSS of scal, bitwise the values a full evaluation of
 // the same point writes (same partials, same reduction order). The forward state stays for
-// grad_after_loss. lambda must be 0 (the L-BFGS objectives).
+// grad_after_loss. lambda != 0: the penalty 0.5 lambda w.w from the point's w.w partials (no w.w of the trial
+// point exists otherwise before the backward), which the following grad_after_loss must be given too.
 void Mlp::loss_only(const float *P, const float *X, const float *Y, const int *idx, long long B, double inv_scale,
-                    double *scal) {
+                    double *scal, double lambda, WwPart ww) {
   LBF_REQUIRE(B >= 0, "negative batch");
+  LBF_REQUIRE(lambda == 0.0 || ww.part, "loss_only: a penalised loss needs the point's w.w partials");
   hipStream_t s = ctx_->stream;
   const float *hilo = nullptr;
   if (B > 0) forward_phase(P, X, Y, idx, B, inv_scale);
@@ -526,15 +534,16 @@ void Mlp::loss_only(const float *P, const float *X, const float *Y, const int *i
     hilo = hilo_.get();
   }
   ProfScope ps(ctx_, PK_FINAL, 2);
-  sse_loss(s, loss_part_.get(), B > 0 ? fs_.nloss : 0, hilo, inv_scale, scal, ctx_->abort);
+  sse_loss(s, loss_part_.get(), B > 0 ? fs_.nloss : 0, hilo, inv_scale, scal, ctx_->abort, lambda, ww);
   ++loss_only_;
 }
 
 void Mlp::loss_grad(const float *P, float *G, const float *X, const float *Y, const int *idx, long long B,
-                    double inv_scale, double lambda, const float *pdir, double *scal, const TailFuse *tf) {
+                    double inv_scale, double lambda, const float *pdir, double *scal, const TailFuse *tf,
+                    WwPart ww) {
   LBF_REQUIRE(B >= 0, "negative batch");
   if (B > 0) forward_phase(P, X, Y, idx, B, inv_scale);
-  backward_phase(P, G, X, idx, B, inv_scale, lambda, pdir, scal, tf, false, nullptr);
+  backward_phase(P, G, X, idx, B, inv_scale, lambda, pdir, scal, tf, false, nullptr, nullptr, ww);
 }
 
 void Mlp::loss_grad_deferred(const float *P, float *G, const float *X, const float *Y, const int *idx, long long B,
@@ -554,21 +563,23 @@ void Mlp::loss_grad_local(const float *P, float *G, const float *X, const float 
 }
 
 void Mlp::grad_after_loss(const float *P, float *G, const float *X, const int *idx, long long B, double inv_scale,
-                          double lambda, const float *pdir, double *scal, const TailFuse *tf) {
+                          double lambda, const float *pdir, double *scal, const TailFuse *tf, WwPart ww) {
   LBF_REQUIRE(B == 0 || fs_.B == B, "grad_after_loss: no forward phase of this batch");
   ++gal_;
   // the reduced route reports the loss of the loss-only trial's own all-reduced words, so the Armijo
   // decision and the recorded loss are one value whatever order the collective sums the two buffers in
   const bool reduced = ctx_->dp() || B == 0;
-  backward_phase(P, G, X, idx, B, inv_scale, lambda, pdir, scal, tf, false, reduced ? hilo_.get() : nullptr);
+  backward_phase(P, G, X, idx, B, inv_scale, lambda, pdir, scal, tf, false, reduced ? hilo_.get() : nullptr, nullptr,
+                 ww);
 }
 
 // Backward phase: the dW / dX GEMMs below the head, every layer's slab reduction, the gradient
 // finish (+ all-reduce, dots, status block) or the fused optimizer tail.
 void Mlp::backward_phase(const float *P, float *G, const float *X, const int *idx, long long B, double inv_scale,
                          double lambda, const float *pdir, double *scal, const TailFuse *tf, bool local,
-                         const float *hilo_in, RedAllArgs *defer) {
+                         const float *hilo_in, RedAllArgs *defer, WwPart ww) {
   hipStream_t s = ctx_->stream;
+  if (lambda == 0.0) ww = {}; // no penalty: the lambda = 0 kernels
   const int nl = int(layers_.size());
   const Layer &Lo = layers_[nl - 1];
   const bool empty = B == 0; // a data-parallel rank whose share of a small batch is empty
@@ -662,16 +673,19 @@ void Mlp::backward_phase(const float *P, float *G, const float *X, const int *id
     x.tile = dx_tile(B, L.in);
     return x;
   };
-  // A speculative first trial (tf->early: single rank, lambda = 0) takes its Armijo test in the first backward
+  // A speculative first trial (tf->early: single rank; lambda != 0 with the point's w.w partials) takes its Armijo test in the first backward
   // launch (EarlyLs, gemm.hip gemm_early_exit): on a failure that launch, the rest of the backward and the tail
   // exit at entry, and the host finishes the search as after the tail's own rejection (LBF_NO_EARLY=1: off).
   const bool early_on = env_int("LBF_NO_EARLY", 0) == 0; // read per evaluation: tests switch it in-process
   EarlyLs early;
   const EarlyLs *early_p = nullptr;
-  if (early_on && tf && tf->early && !reduced && lambda == 0.0 && nloss > 0) {
+  if (early_on && tf && tf->early && !reduced && (lambda == 0.0 || ww.part) && nloss > 0) {
     early.sse_part = loss_part_.get();
     early.nsse = nloss;
     early.inv_scale = inv_scale;
+    early.ww_part = ww.part;
+    early.nww = ww.n;
+    early.lambda = lambda;
     early.ls = tf->ls;
     early_p = &early;
   }
@@ -722,6 +736,8 @@ void Mlp::backward_phase(const float *P, float *G, const float *X, const int *id
   ra.inv_scale = inv_scale;
   ra.scal = scal;
   ra.abort = ctx_->abort;
+  ra.ww_part = ww.part;
+  ra.nww = ww.n;
   for (int l = 0; l < nl; ++l) {
     const Layer &L = layers_[l];
     RedSeg &g = ra.seg[l];
@@ -841,7 +857,7 @@ void Mlp::backward_phase(const float *P, float *G, const float *X, const int *id
     ProfScope ps(ctx_, PK_ALLREDUCE);
     ctx_->allreduce(Gl, nparams_ + 2); // one RCCL all-reduce of [grad | sse_hi | sse_lo]
   }
-  finish_reduced(P, G, inv_scale, lambda, pdir, scal, hilo_in, Gl != G ? Gl : nullptr);
+  finish_reduced(P, G, inv_scale, lambda, pdir, scal, hilo_in, Gl != G ? Gl : nullptr, ww);
 }
 
 void Mlp::batch_grads(const float *P, const float *X, const float *Y, int nmb, long long cnt, double inv_scale,
@@ -919,7 +935,7 @@ void Mlp::batch_grads(const float *P, const float *X, const float *Y, int nmb, l
 // The gradient and status of an all-reduced [G | hi | lo] block: G += lambda w, the dots of the status
 // block, and the loss from the (hi, lo) words (or from hilo_in: a loss-only trial's reduced words).
 void Mlp::finish_reduced(const float *P, float *G, double inv_scale, double lambda, const float *pdir, double *scal,
-                         const float *hilo_in, const float *g_src) {
+                         const float *hilo_in, const float *g_src, WwPart ww) {
   hipStream_t s = ctx_->stream;
   ProfScope ps(ctx_, PK_FINAL, 1);
   const int nd = dots_partials_wg(nparams_);
@@ -927,7 +943,7 @@ void Mlp::finish_reduced(const float *P, float *G, double inv_scale, double lamb
   finalize_grad_dots(s, nparams_, G, P, lambda, pdir, dots_part_.get(), ctx_->abort, g_src);
   if (scal)
     eval_tail(s, dots_part_.get(), nd, loss_part_.get(), 0, hilo_in ? hilo_in : (g_src ? g_src : G) + nparams_,
-              inv_scale, lambda, scal, ctx_->abort);
+              inv_scale, lambda, scal, ctx_->abort, ww);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1287,8 +1303,9 @@ bool History::update_combine(const GramArgs &g0, int iter, double dsign, const f
 }
 
 void History::combine(const float *g, float *dir, const float *x_in, float *x_out, float *x_out2,
-                      bool alpha_from_state, double alpha) {
+                      bool alpha_from_state, double alpha, double *ww_part) {
   CombineArgs a;
+  a.ww_part = ww_part;
   a.h = v_;
   a.h.abort = ctx_->abort;
   a.g = g;

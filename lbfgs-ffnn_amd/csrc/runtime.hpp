@@ -121,6 +121,11 @@ public:
   // at least two outputs. Takes effect from the next evaluation; the workspace and the plan do not depend on it.
   void set_loss(int loss);
   int loss() const { return loss_; }
+  // L2 weight decay of the solvers that take no lambda of their own (full-batch L-BFGS, GD, SGD): they minimise
+  // data loss + 0.5 l2 |w|^2. A property of the network like the loss; read when a solve begins. The evaluations
+  // below take their lambda as an argument and do not read it.
+  void set_l2(double l2);
+  double l2() const { return l2_; }
 
   // Forward only: activations of every layer into the workspace; returns the output buffer.
   // raw_last: the last layer run stays as its split-K slabs in fslab_buf(l) (no fwd_reduce_act; rowhead reads them)
@@ -132,7 +137,8 @@ public:
   //   pdir : optional direction for the g.p dot.
   //   scal : device fp64 status block (SC_LOSS, SC_TGG, SC_TGP, SC_WW, SC_SSE written).
   void loss_grad(const float *P, float *G, const float *X, const float *Y, const int *idx, long long B,
-                 double inv_scale, double lambda, const float *pdir, double *scal, const TailFuse *tf = nullptr);
+                 double inv_scale, double lambda, const float *pdir, double *scal, const TailFuse *tf = nullptr,
+                 WwPart ww = {});
   // loss_grad without the last launch (a single rank's gradient only: scal == nullptr): the split-K slabs
   // are left for the consumer, which finishes each gradient value with reduce_all's arithmetic (the S-LBFGS
   // direction sweep, dir.hip). *red describes the slabs; red->nseg == 0 when a segment needs the multi-part
@@ -143,12 +149,14 @@ public:
                           double inv_scale, double lambda, RedAllArgs *red);
   // The same evaluation in two steps (a line-search trial needs f first and the gradient only once
   // Armijo holds, full_batch_minimizer.hpp:136-146): loss_only runs the forward phase and writes
-  // SC_SSE / SC_LOSS (lambda == 0); grad_after_loss then runs the backward phase of that same forward
-  // state. loss_only followed by grad_after_loss == loss_grad, bit for bit.
+  // SC_SSE / SC_LOSS; grad_after_loss then runs the backward phase of that same forward state. loss_only
+  // followed by grad_after_loss == loss_grad, bit for bit. ww: the w.w partials of P (kernels.hpp WwPart), from
+  // which every evaluation of P takes SC_WW and the penalty when lambda != 0 (loss_only requires them then: it
+  // has no sweep over P of its own); without them a full evaluation uses its own sweep's w.w.
   void loss_only(const float *P, const float *X, const float *Y, const int *idx, long long B, double inv_scale,
-                 double *scal);
+                 double *scal, double lambda = 0.0, WwPart ww = {});
   void grad_after_loss(const float *P, float *G, const float *X, const int *idx, long long B, double inv_scale,
-                       double lambda, const float *pdir, double *scal, const TailFuse *tf = nullptr);
+                       double lambda, const float *pdir, double *scal, const TailFuse *tf = nullptr, WwPart ww = {});
   // Packed data-parallel evaluation in two halves: loss_grad_local stops before the all-reduce, leaving
   // this rank's gradient (no lambda w) and its SSE as fp32 (hi, lo) words in G[0 .. n+2); the caller
   // all-reduces one or more such blocks in a single collective and then finishes each with
@@ -157,7 +165,7 @@ public:
                        double inv_scale);
   // g_src (nullable): the reduced words are there and the finished gradient is written to G
   void finish_reduced(const float *P, float *G, double inv_scale, double lambda, const float *pdir, double *scal,
-                      const float *hilo_in = nullptr, const float *g_src = nullptr);
+                      const float *hilo_in = nullptr, const float *g_src = nullptr, WwPart ww = {});
   // Per-minibatch gradients at one point P (S-LBFGS's anchor gradients: w is fixed for an epoch): rows
   // [t cnt, (t+1) cnt) of the gathered X / Y are minibatch t (t < nmb); its gradient, scaled by inv_scale,
   // goes to G + t ldg (+ lambda P unless local: a data-parallel rank's partial sums). One evaluation over
@@ -186,7 +194,7 @@ private:
   void forward_phase(const float *P, const float *X, const float *Y, const int *idx, long long B, double inv_scale);
   void backward_phase(const float *P, float *G, const float *X, const int *idx, long long B, double inv_scale,
                       double lambda, const float *pdir, double *scal, const TailFuse *tf, bool local,
-                      const float *hilo_in, RedAllArgs *defer = nullptr);
+                      const float *hilo_in, RedAllArgs *defer = nullptr, WwPart ww = {});
   struct FwdState {
     long long B = -1;
     bool fused = false;
@@ -203,6 +211,7 @@ private:
   std::vector<Layer> layers_;
   size_t nparams_ = 0;
   int loss_ = LOSS_MSE;
+  double l2_ = 0.0;
   // the output layer on the generic route: loss_diff or loss_xent on A_[nl - 1] -> D_[nl - 1], loss_part_
   void out_loss(const float *Y, const int *idx, long long B, double inv_scale);
   long long cap_ = -1, planned_ = -1;
@@ -243,8 +252,9 @@ public:
   void update(const GramArgs &g, int want_dir, int iter, double dsign, const RedAllArgs *gred = nullptr) {
     (void)update_impl(g, want_dir, iter, dsign, gred, nullptr);
   }
+  // ww_part (nullable): also x_out's w.w partials (kernels.hpp WwPart)
   void combine(const float *g, float *dir, const float *x_in, float *x_out, float *x_out2, bool alpha_from_state,
-               double alpha);
+               double alpha, double *ww_part = nullptr);
   // update(g, 1, iter, dsign) then combine(g.g_out, nullptr, x_in, x_out, x_out2, false, alpha)
   bool update_combine(const GramArgs &g, int iter, double dsign, const float *x_in, float *x_out, float *x_out2,
                       double alpha, const RedAllArgs *gred = nullptr);

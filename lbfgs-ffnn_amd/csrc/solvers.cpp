@@ -66,11 +66,15 @@ LbfgsSolver::LbfgsSolver(Objective *obj, const lbf_lbfgs_params &prm, float *d_p
     std::memset(spec_rec_, 0xff, kSpecRing * sizeof(SpecRecord));
   }
   LBF_HIP(hipMemcpyAsync(x_, d_params, size_t(n_) * sizeof(float), hipMemcpyDeviceToDevice, ctx_->stream));
+  l2_on_ = obj_->l2() != 0.0;
+  if (l2_on_)
+    for (int i = 0; i < 3; ++i) wwbuf_[i].resize(size_t(ww_partials_n(n_)));
   evals0_ = obj_->evals();
   rows0_ = obj_->rows();
   lonly0_ = obj_->loss_only_evals();
   gal0_ = obj_->grad_after_loss_evals();
-  // initial evaluation (lbfgs.hpp:44 / lbfgs.cuh:147)
+  // initial evaluation (lbfgs.hpp:44 / lbfgs.cuh:147); under weight decay the start point has no w.w partials
+  // (no combine wrote it) and no loss-only or early twin: its w.w is the evaluation's own sweep
   eval(x_, g_, nullptr);
   read_status();
   loss_ = hs_[SC_LOSS];
@@ -83,7 +87,29 @@ LbfgsSolver::~LbfgsSolver() {
   if (spec_rec_) (void)hipHostFree(spec_rec_);
 }
 
-void LbfgsSolver::eval(const float *x, float *g, const float *pdir) { obj_->eval(x, g, pdir, hist_.scal()); }
+int LbfgsSolver::xslot(const float *x) const {
+  for (int i = 0; i < 3; ++i)
+    if (x == xbuf_[i].get()) return i;
+  throw Error(2, "L-BFGS: not one of the solver's point buffers");
+}
+
+double *LbfgsSolver::ww_out(const float *x) {
+  if (!l2_on_) return nullptr;
+  const int i = xslot(x);
+  ww_valid_[i] = true;
+  return wwbuf_[i].get();
+}
+
+void LbfgsSolver::announce_ww(const float *x) {
+  if (!l2_on_) return;
+  const int i = xslot(x);
+  obj_->point_ww(ww_valid_[i] ? wwbuf_[i].get() : nullptr);
+}
+
+void LbfgsSolver::eval(const float *x, float *g, const float *pdir) {
+  announce_ww(x);
+  obj_->eval(x, g, pdir, hist_.scal());
+}
 
 void LbfgsSolver::read_status() {
   LBF_HIP(hipMemcpyAsync(hs_.get(), hist_.scal(), SC_N * sizeof(double), hipMemcpyDeviceToHost, ctx_->stream));
@@ -157,7 +183,8 @@ float LbfgsSolver::begin_iteration(const LsCtlArgs *ls) {
   const bool armijo = prm_.line_search == LBF_LS_ARMIJO;
   if (ls && dir_ready_) { // the previous fused tail computed this direction's coefficients
     float alpha = 1.0f;
-    hist_.combine(g_, p_.get(), x_, xt_, nullptr, !armijo, armijo ? double(alpha) : 0.0);
+    hist_.combine(g_, p_.get(), x_, xt_, nullptr, !armijo, armijo ? double(alpha) : 0.0, ww_out(xt_));
+    announce_ww(xt_);
     TailFuse tf;
     tf.h = hist_.view();
     tf.has_pair = prm_.m > 0;
@@ -187,9 +214,9 @@ float LbfgsSolver::begin_iteration(const LsCtlArgs *ls) {
   float alpha = 1.0f;
   if (armijo) {
     if (iter_ == 0) alpha = std::min(1.0f, 1.0f / float(std::sqrt(gg_))); // lbfgs.cuh:149
-    hist_.combine(g_, p_.get(), x_, xt_, nullptr, false, double(alpha));
+    hist_.combine(g_, p_.get(), x_, xt_, nullptr, false, double(alpha), ww_out(xt_));
   } else {
-    hist_.combine(g_, p_.get(), x_, xt_, nullptr, true, 0.0); // xt = x + alpha0 p
+    hist_.combine(g_, p_.get(), x_, xt_, nullptr, true, 0.0, ww_out(xt_)); // xt = x + alpha0 p
   }
   if (ls) {
     TailFuse tf;
@@ -202,6 +229,7 @@ float LbfgsSolver::begin_iteration(const LsCtlArgs *ls) {
     tf.ls = *ls;
     tf.ls.alphaf = alpha;
     tf.early = ls->first ? 0 : 1; // (Wolfe iteration 0 takes its trial without a test)
+    announce_ww(xt_);
     obj_->eval_fused(xt_, gt_, p_.get(), hist_.scal(), tf);
   } else {
     eval(xt_, gt_, p_.get());
@@ -245,6 +273,7 @@ int LbfgsSolver::grad_fused(double alpha, SpecRecord *r) {
   tf.iter_next = iter_ + 1;
   tf.ls = a;
   tf.ls.alphaf = float(alpha); // Armijo: the fp32 trial step itself
+  announce_ww(xt_);
   obj_->eval_grad_after_loss_fused(xt_, gt_, p_.get(), hist_.scal(), tf);
   wait_record(a.seq, r);
   if (r->seq != a.seq) throw Error(2, "speculative line search: record out of sequence");
@@ -268,9 +297,10 @@ void LbfgsSolver::finish_wolfe(lbf_record *rec, bool spec) {
       if (!evaluated) {
         {
           ProfScope ps(ctx_, PK_AXPY);
-          axpy_to(ctx_->stream, n_, x_, float(alpha), p_.get(), xt_);
+          axpy_to(ctx_->stream, n_, x_, float(alpha), p_.get(), xt_, ww_out(xt_));
         }
         if (split) { // f(x + alpha p) first; the gradient only once Armijo holds (:136-146)
+          announce_ww(xt_);
           obj_->eval_loss(xt_, hist_.scal());
           have_grad = false;
         } else {
@@ -296,6 +326,7 @@ void LbfgsSolver::finish_wolfe(lbf_record *rec, bool spec) {
           }
           read_status(); // rejected on curvature (or converged): the host's search goes on from the status
         } else {
+          announce_ww(xt_);
           obj_->eval_grad_after_loss(xt_, gt_, p_.get(), hist_.scal());
           read_status();
         }
@@ -310,10 +341,11 @@ void LbfgsSolver::finish_wolfe(lbf_record *rec, bool spec) {
       break;
     }
     if (!evaluated) { // exhausted: the returned alpha was never evaluated (lbfgs.hpp:67-70)
-      axpy_to(ctx_->stream, n_, x_, float(alpha), p_.get(), xt_);
+      axpy_to(ctx_->stream, n_, x_, float(alpha), p_.get(), xt_, ww_out(xt_));
       eval(xt_, gt_, p_.get());
       read_status();
     } else if (!have_grad) { // exhausted on an Armijo failure: x_new's gradient is still needed
+      announce_ww(xt_);
       obj_->eval_grad_after_loss(xt_, gt_, p_.get(), hist_.scal());
       read_status();
     }
@@ -352,8 +384,9 @@ void LbfgsSolver::finish_armijo(float alpha, lbf_record *rec, bool spec) {
   bool have_grad = true;
   for (int ls = 0; ls < prm_.max_line_iters; ++ls) {
     if (ls > 0) { // loss only; the accepted (or last) trial's gradient afterwards (lbfgs.cuh:115-140)
-      axpy_to(ctx_->stream, n_, x_, alpha, p_.get(), xt_);
+      axpy_to(ctx_->stream, n_, x_, alpha, p_.get(), xt_, ww_out(xt_));
       if (split) {
+        announce_ww(xt_);
         obj_->eval_loss(xt_, hist_.scal());
         have_grad = false;
       } else {
@@ -385,7 +418,10 @@ void LbfgsSolver::finish_armijo(float alpha, lbf_record *rec, bool spec) {
     if (spec && fuse_ && ok && grad_fused(double(a_eval), &fr) == SPEC_ACCEPT) {
       fused_done = true;
     } else {
-      if (!(spec && fuse_ && ok)) obj_->eval_grad_after_loss(xt_, gt_, p_.get(), hist_.scal());
+      if (!(spec && fuse_ && ok)) {
+        announce_ww(xt_);
+        obj_->eval_grad_after_loss(xt_, gt_, p_.get(), hist_.scal());
+      }
       read_status(); // (after a fused tail that did not accept: its status block)
     }
   }
@@ -1274,8 +1310,9 @@ int run_gd(Mlp *net, const lbf_gd_params &prm, float *d_params, const float *X, 
   hs.ensure(SC_N);
   LBF_HIP(hipMemsetAsync(v.get(), 0, size_t(n) * sizeof(float), s));
   const long long evals0 = net->evals(), rows0 = net->rows();
+  const double l2 = net->l2(); // weight decay: loss + 0.5 l2 |w|^2, g + l2 w (the evaluation's finalize path)
   auto eval = [&]() {
-    net->loss_grad(d_params, g.get(), X, Y, nullptr, n_local, 1.0 / double(n_global), 0.0, nullptr, scal.get());
+    net->loss_grad(d_params, g.get(), X, Y, nullptr, n_local, 1.0 / double(n_global), l2, nullptr, scal.get());
     LBF_HIP(hipMemcpyAsync(hs.get(), scal.get(), SC_N * sizeof(double), hipMemcpyDeviceToHost, s));
     LBF_HIP(hipStreamSynchronize(s));
   };
@@ -1303,7 +1340,9 @@ int run_gd(Mlp *net, const lbf_gd_params &prm, float *d_params, const float *X, 
 }
 
 // CudaSGD::solve (sgd.cuh:50-153). Batch losses accumulate on the device (epoch_loss_acc, fp32 like
-// the reference's host sum), so an epoch synchronises once, not once per batch.
+// the reference's host sum), so an epoch synchronises once, not once per batch. Under weight decay (the
+// network's l2) every batch objective is batch loss + 0.5 l2 |w|^2 at the batch's own w, so the epoch loss is the
+// row-weighted mean of the batch objectives, penalty included.
 int run_sgd(Mlp *net, const lbf_sgd_params &prm, float *d_params, const float *X, const float *Y, long long N,
             lbf_record *rec, lbf_solve_info *info) {
   LBF_REQUIRE(d_params && X && Y && N > 0 && prm.batch > 0, "bad argument");
@@ -1321,8 +1360,9 @@ int run_sgd(Mlp *net, const lbf_sgd_params &prm, float *d_params, const float *X
   he.ensure(1);
   LBF_HIP(hipMemsetAsync(v.get(), 0, size_t(n) * sizeof(float), s));
   const long long evals0 = net->evals(), rows0 = net->rows();
+  const double l2 = net->l2();
   auto full = [&]() {
-    net->loss_grad(d_params, g.get(), X, Y, nullptr, N, 1.0 / double(N), 0.0, nullptr, scal.get());
+    net->loss_grad(d_params, g.get(), X, Y, nullptr, N, 1.0 / double(N), l2, nullptr, scal.get());
     LBF_HIP(hipMemcpyAsync(hs.get(), scal.get(), SC_N * sizeof(double), hipMemcpyDeviceToHost, s));
     LBF_HIP(hipStreamSynchronize(s));
   };
@@ -1343,7 +1383,7 @@ int run_sgd(Mlp *net, const lbf_sgd_params &prm, float *d_params, const float *X
     LBF_HIP(hipMemsetAsync(esum.get(), 0, sizeof(float), s));
     for (long long b = 0; b < nb; ++b) { // :107-127
       const long long r0 = b * prm.batch, bs = std::min<long long>(prm.batch, N - r0);
-      net->loss_grad(d_params, g.get(), X + r0 * In, Y + r0 * Out, nullptr, bs, 1.0 / double(bs), 0.0, nullptr,
+      net->loss_grad(d_params, g.get(), X + r0 * In, Y + r0 * Out, nullptr, bs, 1.0 / double(bs), l2, nullptr,
                      scal.get());
       epoch_loss_acc(s, scal.get(), bs, esum.get());
       momentum_step(s, n, mom, cur_lr, nullptr, g.get(), v.get(), d_params);

@@ -28,6 +28,11 @@ struct Objective {
   virtual void eval(const float *x, float *g, const float *pdir, double *scal) = 0;
   virtual long long evals() const = 0;
   virtual long long rows() const { return 0; } // batch rows evaluated (0: not an MLP objective)
+  // L2 weight decay inside the objective (loss + 0.5 l2 |x|^2, g + l2 x). When non-zero, the solver announces
+  // before each evaluation the w.w partials (kernels.hpp WwPart, ww_partials_n(n) words) that the kernel which
+  // wrote the point left, or nullptr for a point no such kernel wrote (the start point).
+  virtual double l2() const { return 0.0; }
+  virtual void point_ww(const double *) {}
   // Asynchronous objectives can be enqueued ahead of the host's line-search decisions.
   virtual bool async() const { return false; }
   virtual void discard_evals(long long) {}
@@ -51,12 +56,19 @@ struct MlpObjective : Objective {
   Mlp *net;
   const float *X, *Y;
   long long nloc, nglob;
+  double lambda; // the network's l2, read once when the solve begins
+  WwPart ww;     // the next evaluated point's w.w partials (point_ww)
   MlpObjective(Mlp *m, const float *x, const float *y, long long nl, long long ng)
-      : net(m), X(x), Y(y), nloc(nl), nglob(ng) {}
+      : net(m), X(x), Y(y), nloc(nl), nglob(ng), lambda(m->l2()) {}
+  double l2() const override { return lambda; }
+  void point_ww(const double *part) override {
+    ww.part = lambda != 0.0 ? part : nullptr;
+    ww.n = ww.part ? ww_partials_n((long long)net->nparams()) : 0;
+  }
   Ctx *ctx() const override { return net->ctx(); }
   long long n() const override { return (long long)net->nparams(); }
   void eval(const float *x, float *g, const float *pdir, double *scal) override {
-    net->loss_grad(x, g, X, Y, nullptr, nloc, 1.0 / double(nglob), 0.0, pdir, scal);
+    net->loss_grad(x, g, X, Y, nullptr, nloc, 1.0 / double(nglob), lambda, pdir, scal, nullptr, ww);
   }
   long long evals() const override { return net->evals(); }
   long long rows() const override { return net->rows(); }
@@ -65,20 +77,20 @@ struct MlpObjective : Objective {
   void backward_skipped() override { net->backward_skipped(); }
   bool split_eval() const override { return true; }
   void eval_loss(const float *x, double *scal) override {
-    net->loss_only(x, X, Y, nullptr, nloc, 1.0 / double(nglob), scal);
+    net->loss_only(x, X, Y, nullptr, nloc, 1.0 / double(nglob), scal, lambda, ww);
   }
   void eval_grad_after_loss(const float *x, float *g, const float *pdir, double *scal) override {
-    net->grad_after_loss(x, g, X, nullptr, nloc, 1.0 / double(nglob), 0.0, pdir, scal);
+    net->grad_after_loss(x, g, X, nullptr, nloc, 1.0 / double(nglob), lambda, pdir, scal, nullptr, ww);
   }
   long long loss_only_evals() const override { return net->loss_only_evals(); }
   long long grad_after_loss_evals() const override { return net->grad_after_loss_evals(); }
   bool fused_tail() const override { return true; }
   void eval_fused(const float *x, float *g, const float *pdir, double *scal, const TailFuse &tf) override {
-    net->loss_grad(x, g, X, Y, nullptr, nloc, 1.0 / double(nglob), 0.0, pdir, scal, &tf);
+    net->loss_grad(x, g, X, Y, nullptr, nloc, 1.0 / double(nglob), lambda, pdir, scal, &tf, ww);
   }
   void eval_grad_after_loss_fused(const float *x, float *g, const float *pdir, double *scal,
                                   const TailFuse &tf) override {
-    net->grad_after_loss(x, g, X, nullptr, nloc, 1.0 / double(nglob), 0.0, pdir, scal, &tf);
+    net->grad_after_loss(x, g, X, nullptr, nloc, 1.0 / double(nglob), lambda, pdir, scal, &tf, ww);
   }
 };
 
@@ -167,6 +179,14 @@ private:
   long long n_;
   History hist_;
   DevBuf<float> xbuf_[3], gbuf_[3], p_;
+  // Weight decay (obj_->l2() != 0): the w.w partials of the point in each x buffer, written by the kernel that
+  // wrote the point (the combine or axpy_to of a trial). They travel with the buffer through the role rotation.
+  DevBuf<double> wwbuf_[3];
+  bool ww_valid_[3] = {false, false, false};
+  bool l2_on_ = false;
+  int xslot(const float *x) const;
+  double *ww_out(const float *x);           // where the producer of x writes (nullptr: no weight decay)
+  void announce_ww(const float *x);         // obj_->point_ww for the evaluation of x that follows
   float *x_, *xp_, *xt_, *g_, *gp_, *gt_;
   PinnedBuf<double> hs_;
   double loss_ = 0, gg_ = 0;

@@ -284,11 +284,16 @@ constexpr int TF_THREADS = 256;
 // Wave 0 (decision, then the recurrences) issues no global store until the coefficients: the status
 // block, the host record (system-scope stores to host-mapped memory, whose acknowledgement the
 // sequence word must wait for) and the history step's ring/Gram writes are made by waves 1..3.
+// WW (lambda != 0 and the point came with w.w partials, ra.ww_part): w.w is the sum of those words (ww_sum: the
+// order sse_loss and the early test use), not this sweep's D[6m + 7], so the loss-only trial, the early test and
+// this decision of one point see the same penalty bits.
+template <bool WW>
 __device__ __forceinline__ void tail_fin_body(const TailArgs &a) {
   const RedAllArgs &ra = a.ra;
   extern __shared__ double dyn[]; // sy [2*m*m] (SY and its transpose) | yy [m*m] | SY, YY [S*S] | rho [S]
   __shared__ HistSmem sm;
   __shared__ double v[4];
+  __shared__ double wwv[WW ? 4 : 1];
   __shared__ double s_rec[4]; // loss, tgg, alpha0, accept_prev
   __shared__ double s_sc[6];  // tgg, tgp, ww, sse, loss, the new f_old
   __shared__ int s_status, s_ok;
@@ -303,6 +308,8 @@ __device__ __forceinline__ void tail_fin_body(const TailArgs &a) {
   double sse = 0.0;
   if (!a.hilo)
     for (int r = t; r < ra.nsse; r += TF_THREADS) sse += ra.sse_part[r];
+  double wwq = 0.0;
+  if constexpr (WW) wwq = ww_sum_wave(ra.ww_part, ra.nww, t); // written by an earlier launch (stream order)
   for (int q = t; q < a.nc; q += TF_THREADS) // sc1 loads: written this launch by other blocks (hand-off)
     sm.dots[q] = __hip_atomic_load(&a.dots[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   for (int i = t; i < S_ * S_; i += TF_THREADS) {
@@ -320,15 +327,23 @@ __device__ __forceinline__ void tail_fin_body(const TailArgs &a) {
   }
   sse = t_wave_sum(sse);
   if (lane == 0) v[wave] = sse;
+  if constexpr (WW)
+    if (lane == 0) wwv[wave] = wwq;
   KTF(45);
   lds_barrier();
   KTF(46);
   if (t == 0) { // decide (LDS only: wave 0 issues no global store before the recurrences)
     const double *D = sm.dots;
     const double sse_t = a.hilo ? (double(a.hilo[0]) + double(a.hilo[1])) : ((v[0] + v[1]) + v[2]) + v[3];
-    const double tgg = D[6 * m + 5], tgp = D[6 * m + 6], ww = D[6 * m + 7];
-    double loss = 0.5 * sse_t * ra.inv_scale;
-    if (ra.lambda != 0.0) loss += 0.5 * ra.lambda * ww;
+    const double tgg = D[6 * m + 5], tgp = D[6 * m + 6];
+    double ww, loss = 0.5 * sse_t * ra.inv_scale;
+    if constexpr (WW) {
+      ww = ww_sum_fin(wwv);
+      loss = ww_loss(loss, ra.lambda, ww);
+    } else {
+      ww = D[6 * m + 7];
+      if (ra.lambda != 0.0) loss += 0.5 * ra.lambda * ww;
+    }
     s_sc[0] = tgg;
     s_sc[1] = tgp;
     s_sc[2] = ww;
@@ -410,6 +425,7 @@ __device__ __forceinline__ void tail_fin_body(const TailArgs &a) {
 // the iteration's critical path. Hand-off without fences (the guide prices __threadfence at ~3.5 us):
 // each block's column sum is an sc1 (write-through) store waited for with vmcnt(0) before the same lane's
 // agent-scope add; the block whose add returns the last count reads the sums with sc1 loads.
+template <bool WW>
 __global__ __launch_bounds__(TF_THREADS) void tail_cols_fin_kernel(const TailArgs a) {
   const int abf = abort_flag(a.ra.abort);
   KT(39);
@@ -421,7 +437,7 @@ __global__ __launch_bounds__(TF_THREADS) void tail_cols_fin_kernel(const TailArg
   __syncthreads();
   if (!s_last) return;
   if (threadIdx.x == 0) *a.cols_done = 0u; // ready for the next launch (stream-ordered)
-  tail_fin_body(a);
+  tail_fin_body<WW>(a);
 }
 
 } // namespace
@@ -463,7 +479,10 @@ void tail_reduce(hipStream_t s, const TailArgs &a) {
   }
   LBF_KERNEL_CHECK();
   if (!a.cols_done) throw Error(2, "tail_reduce: needs the arrival counter (cols_done)");
-  hipLaunchKernelGGL(tail_cols_fin_kernel, dim3(unsigned(a.nc)), dim3(TF_THREADS), fin_shmem(a), s, a);
+  if (a.ra.ww_part && a.ra.lambda != 0.0)
+    hipLaunchKernelGGL(tail_cols_fin_kernel<true>, dim3(unsigned(a.nc)), dim3(TF_THREADS), fin_shmem(a), s, a);
+  else
+    hipLaunchKernelGGL(tail_cols_fin_kernel<false>, dim3(unsigned(a.nc)), dim3(TF_THREADS), fin_shmem(a), s, a);
   LBF_KERNEL_CHECK();
 }
 

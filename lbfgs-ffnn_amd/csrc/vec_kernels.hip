@@ -445,6 +445,8 @@ __global__ __launch_bounds__(256) void reduce_all_kernel(const RedAllArgs a) {
 // the eval_tail reduction. Everything it reads was written by earlier launches (stream order), so it
 // needs no fence.
 constexpr int RF_THREADS = 1024;
+// WW: w.w (SC_WW, the penalty) from the point's partials (a.ww_part, ww_sum) instead of the dot partials
+template <bool WW>
 __global__ __launch_bounds__(RF_THREADS) void reduce_fin_kernel(const RedAllArgs a) {
   if (a.abort && *a.abort) return;
   KT(32);
@@ -486,6 +488,11 @@ __global__ __launch_bounds__(RF_THREADS) void reduce_fin_kernel(const RedAllArgs
     const double w = wave_sum(acc[i]);
     if (lane == 0) ws[wave][i] = w;
   }
+  __shared__ double wwv[WW ? 4 : 1];
+  if constexpr (WW) {
+    const double w = ww_sum_wave(a.ww_part, a.nww, t);
+    if (lane == 0 && wave < 4) wwv[wave] = w;
+  }
   __syncthreads();
   if (t < 4) {
     double x = 0.0;
@@ -497,10 +504,16 @@ __global__ __launch_bounds__(RF_THREADS) void reduce_fin_kernel(const RedAllArgs
     double *sc = a.scal;
     sc[SC_TGG] = v[0];
     sc[SC_TGP] = v[1];
-    sc[SC_WW] = v[2];
     sc[SC_SSE] = v[3];
     double loss = 0.5 * v[3] * a.inv_scale;
-    if (a.lambda != 0.0) loss += 0.5 * a.lambda * v[2];
+    if constexpr (WW) {
+      const double ww = ww_sum_fin(wwv);
+      sc[SC_WW] = ww;
+      loss = ww_loss(loss, a.lambda, ww);
+    } else {
+      sc[SC_WW] = v[2];
+      if (a.lambda != 0.0) loss += 0.5 * a.lambda * v[2];
+    }
     sc[SC_LOSS] = loss;
   }
   KT(35);
@@ -509,28 +522,47 @@ __global__ __launch_bounds__(RF_THREADS) void reduce_fin_kernel(const RedAllArgs
 // Forward-only loss of a line-search trial: the SSE partials summed exactly as reduce_fin_kernel sums
 // them (same threads, same strided rows, same wave and cross-wave order), so the loss is bitwise the
 // one the full evaluation of the same point reports; data parallel: from the all-reduced (hi, lo).
+template <bool WW>
 __global__ __launch_bounds__(RF_THREADS) void sse_loss_kernel(const double *sse_part, int nsse, const float *hilo,
-                                                              double inv_scale, double *scal, const int *abort) {
+                                                              double inv_scale, double *scal, const int *abort,
+                                                              double lambda, const double *ww_part, int nww) {
   if (abort && *abort) return;
   __shared__ double ws[RF_THREADS / 64];
+  __shared__ double wwv[WW ? 4 : 1];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   double acc = 0.0;
   if (!hilo)
     for (int r = t; r < nsse; r += RF_THREADS) acc += sse_part[r];
   const double w = wave_sum(acc);
   if (lane == 0) ws[wave] = w;
+  if constexpr (WW) {
+    const double q = ww_sum_wave(ww_part, nww, t);
+    if (lane == 0 && wave < 4) wwv[wave] = q;
+  }
   __syncthreads();
   if (t == 0) {
     double x = 0.0;
     for (int i = 0; i < RF_THREADS / 64; ++i) x += ws[i];
     const double sse = hilo ? (double(hilo[0]) + double(hilo[1])) : x;
     scal[SC_SSE] = sse;
-    scal[SC_LOSS] = 0.5 * sse * inv_scale;
+    if constexpr (WW) {
+      const double ww = ww_sum_fin(wwv);
+      scal[SC_WW] = ww;
+      scal[SC_LOSS] = ww_loss(0.5 * sse * inv_scale, lambda, ww);
+    } else {
+      scal[SC_LOSS] = 0.5 * sse * inv_scale;
+    }
   }
 }
 void sse_loss(hipStream_t s, const double *sse_part, int nsse, const float *hilo, double inv_scale, double *scal,
-              const int *abort) {
-  hipLaunchKernelGGL(sse_loss_kernel, dim3(1), dim3(RF_THREADS), 0, s, sse_part, nsse, hilo, inv_scale, scal, abort);
+              const int *abort, double lambda, WwPart ww) {
+  LBF_REQUIRE(lambda == 0.0 || ww.part, "sse_loss: a penalised loss needs the point's w.w partials");
+  if (lambda != 0.0)
+    hipLaunchKernelGGL(sse_loss_kernel<true>, dim3(1), dim3(RF_THREADS), 0, s, sse_part, nsse, hilo, inv_scale, scal,
+                       abort, lambda, ww.part, ww.n);
+  else
+    hipLaunchKernelGGL(sse_loss_kernel<false>, dim3(1), dim3(RF_THREADS), 0, s, sse_part, nsse, hilo, inv_scale, scal,
+                       abort, 0.0, (const double *)nullptr, 0);
   LBF_KERNEL_CHECK();
 }
 
@@ -539,7 +571,10 @@ void reduce_all(hipStream_t s, const RedAllArgs &a) {
   hipLaunchKernelGGL(reduce_all_kernel, dim3(unsigned(a.nwg + (a.sse_hilo ? 1 : 0))), dim3(256), 0, s, a);
   LBF_KERNEL_CHECK();
   if (a.nfin > 0 || a.dots) {
-    hipLaunchKernelGGL(reduce_fin_kernel, dim3(1), dim3(RF_THREADS), 0, s, a);
+    if (a.ww_part && a.lambda != 0.0 && a.dots)
+      hipLaunchKernelGGL(reduce_fin_kernel<true>, dim3(1), dim3(RF_THREADS), 0, s, a);
+    else
+      hipLaunchKernelGGL(reduce_fin_kernel<false>, dim3(1), dim3(RF_THREADS), 0, s, a);
     LBF_KERNEL_CHECK();
   }
 }
@@ -659,6 +694,48 @@ __global__ __launch_bounds__(256) void axpy_to_kernel(long long n, const float *
     for (long long j = e; j < n; ++j) y[j] = x[j] + alpha * p[j];
   }
 }
+// w.w partials (kernels.hpp WwPart): one word per block of E = ww_block_elems(n) elements.
+long long ww_block_elems(long long n) {
+  long long e = 256;
+  while (cdiv(n, e) > 8192) e *= 2;
+  return e;
+}
+int ww_partials_n(long long n) { return int(std::max(1LL, cdiv(n, ww_block_elems(n)))); }
+// A 256-thread block's fp64 sum in a fixed order (wave sums, then ((v0 + v1) + v2) + v3), stored by thread 0
+// with an ordinary store.
+__device__ __forceinline__ void ww_block_store(double q, double *part) {
+  __shared__ double wv[4];
+  q = wave_sum(q);
+  if ((threadIdx.x & 63) == 0) wv[threadIdx.x >> 6] = q;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = ((wv[0] + wv[1]) + wv[2]) + wv[3];
+}
+// block b: elements [b E, (b + 1) E), thread t the elements b E + t, + 256, .. in order
+__global__ __launch_bounds__(256) void ww_partials_kernel(long long n, long long E, const float *x, double *part,
+                                                          const int *abort) {
+  if (abort && *abort) return;
+  const long long e0 = (long long)blockIdx.x * E, e1 = e0 + E < n ? e0 + E : n;
+  double q = 0.0;
+  for (long long e = e0 + threadIdx.x; e < e1; e += 256) q += double(x[e]) * double(x[e]);
+  ww_block_store(q, part);
+}
+void ww_partials(hipStream_t s, long long n, const float *x, double *part, const int *abort) {
+  hipLaunchKernelGGL(ww_partials_kernel, dim3(unsigned(ww_partials_n(n))), dim3(256), 0, s, n, ww_block_elems(n), x,
+                     part, abort);
+  LBF_KERNEL_CHECK();
+}
+// axpy_to that also writes y's w.w partials (E == 256: one element per thread, one word per block)
+__global__ __launch_bounds__(256) void axpy_to_ww_kernel(long long n, const float *x, float alpha, const float *p,
+                                                         float *y, double *part) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  double q = 0.0;
+  if (e < n) {
+    const float o = x[e] + alpha * p[e];
+    y[e] = o;
+    q = double(o) * double(o);
+  }
+  ww_block_store(q, part);
+}
 // GD / SGD step (gd.cuh:77-85, sgd.cuh:115-124): v = m v - lr g ; x += v (m > 0), else x -= lr g. The
 // reference's scal + two cuBLAS saxpys in one pass: v*m rounded, then the saxpys' fused multiply-adds.
 // lr is read from the device (SGD's decayed rate lives there) when lr_dev is non-null.
@@ -693,9 +770,16 @@ void epoch_loss_acc(hipStream_t s, const double *scal, long long rows, float *es
   LBF_KERNEL_CHECK();
 }
 
-void axpy_to(hipStream_t s, long long n, const float *x, float alpha, const float *p, float *y) {
+void axpy_to(hipStream_t s, long long n, const float *x, float alpha, const float *p, float *y, double *ww_part) {
+  if (ww_part && ww_block_elems(n) == 256) {
+    hipLaunchKernelGGL(axpy_to_ww_kernel, dim3(unsigned(ww_partials_n(n))), dim3(256), 0, s, n, x, alpha, p, y,
+                       ww_part);
+    LBF_KERNEL_CHECK();
+    return;
+  }
   hipLaunchKernelGGL(axpy_to_kernel, dim3(unsigned(cdiv(cdiv(n, 4), 256))), dim3(256), 0, s, n, x, alpha, p, y);
   LBF_KERNEL_CHECK();
+  if (ww_part) ww_partials(s, n, y, ww_part); // large n: the partials of wider blocks in a launch of their own
 }
 void axpy(hipStream_t s, long long n, float alpha, const float *x, float *y) { axpy_to(s, n, y, alpha, x, y); }
 
@@ -1514,7 +1598,8 @@ __global__ __launch_bounds__(256) void combine_chunk_kernel(const CombineArgs a)
 // the grid covers every CU, the ring header and coefficients read lane-distributed (no LDS, no
 // barrier) and broadcast with v_readlane, and every history load of the lane issued at once: one
 // round trip for the header, one for the data.
-template <int KMAX>
+// WW: x_out's w.w partials (one word per block: 256 elements == ww_block_elems(n) for every n of this form).
+template <int KMAX, bool WW = false>
 __global__ __launch_bounds__(256) void combine_small_kernel(const CombineArgs a) {
   // the speculative chain's abort flag: requested with the header, g and x (one round trip for all) and
   // tested before the history loads, so an aborted launch exits after that round trip
@@ -1547,6 +1632,16 @@ __global__ __launch_bounds__(256) void combine_small_kernel(const CombineArgs a)
 #pragma unroll
   for (int i = 0; i < KMAX; ++i)
     if (i < k) acc += lane_f64(csr, i) * double(sv[i]) + lane_f64(cyr, i) * double(yv[i]);
+  if constexpr (WW) {
+    const float d = float(acc), o = xv + float(alpha) * d;
+    if (in) {
+      if (a.dir) a.dir[e] = d;
+      a.x_out[e] = o;
+      if (a.x_out2) a.x_out2[e] = o;
+    }
+    ww_block_store(in ? double(o) * double(o) : 0.0, a.ww_part);
+    return;
+  }
   if (!in) return;
   const float d = float(acc);
   if (a.dir) a.dir[e] = d;
@@ -1557,17 +1652,31 @@ __global__ __launch_bounds__(256) void combine_small_kernel(const CombineArgs a)
   }
 }
 
-void hist_combine(hipStream_t s, const CombineArgs &a) {
-  LBF_REQUIRE(a.h.ld % 4 == 0, "history slot stride must be a multiple of 4");
-  if (a.h.n <= (1LL << 21) && a.h.m <= 32) {
-    const dim3 g1(unsigned(cdiv(a.h.n, 256)));
-    if (a.h.m <= 16)
-      hipLaunchKernelGGL(combine_small_kernel<16>, g1, dim3(256), 0, s, a);
+static void combine_stream(hipStream_t s, const CombineArgs &a); // n > 2^21 or m > 32
+
+void hist_combine(hipStream_t s, const CombineArgs &ca) {
+  LBF_REQUIRE(ca.h.ld % 4 == 0, "history slot stride must be a multiple of 4");
+  LBF_REQUIRE(!ca.ww_part || ca.x_out, "hist_combine: w.w partials need x_out");
+  if (ca.h.n <= (1LL << 21) && ca.h.m <= 32) {
+    const dim3 g1(unsigned(cdiv(ca.h.n, 256)));
+    if (ca.ww_part) {
+      if (ca.h.m <= 16)
+        hipLaunchKernelGGL((combine_small_kernel<16, true>), g1, dim3(256), 0, s, ca);
+      else
+        hipLaunchKernelGGL((combine_small_kernel<32, true>), g1, dim3(256), 0, s, ca);
+    } else if (ca.h.m <= 16)
+      hipLaunchKernelGGL((combine_small_kernel<16>), g1, dim3(256), 0, s, ca);
     else
-      hipLaunchKernelGGL(combine_small_kernel<32>, g1, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((combine_small_kernel<32>), g1, dim3(256), 0, s, ca);
     LBF_KERNEL_CHECK();
     return;
   }
+  // the streaming forms: x_out's partials in a launch of their own behind the combine (abort-aware like it)
+  combine_stream(s, ca);
+  if (ca.ww_part) ww_partials(s, ca.h.n, ca.x_out, ca.ww_part, ca.h.abort);
+}
+
+static void combine_stream(hipStream_t s, const CombineArgs &a) {
   static const int chunked = env_int("LBF_COMBINE_CHUNK", 1); // A/B: 0 keeps combine_kernel
   if (chunked) {
     // 2 vectors x 4 quads in flight per lane: measured against 1 x 4, 2 x 2 and 4 x 2 (m = 50: 69.9-70.0 % against
@@ -1619,11 +1728,14 @@ void hist_reset(hipStream_t s, const HistView &h) {
 // Evaluation tail (one workgroup): fixed-order reductions of the finalize dots (g.g, g.p, w.w) and,
 // on a single rank, of the SSE partials; then the loss (0.5*sse*inv_scale + 0.5*lambda*w.w).
 // ---------------------------------------------------------------------------------------------
+template <bool WW>
 __global__ __launch_bounds__(256) void eval_tail_kernel(const double *dots_part, int nd, const double *sse_part,
                                                         int nsse, const float *hilo, double inv_scale,
-                                                        double lambda, double *scal, const int *abort) {
+                                                        double lambda, double *scal, const int *abort,
+                                                        const double *ww_part, int nww) {
   if (abort && *abort) return;
   __shared__ double v[4];
+  __shared__ double wwv[WW ? 4 : 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double s = 0.0;
   if (wave < 3) {
@@ -1633,23 +1745,37 @@ __global__ __launch_bounds__(256) void eval_tail_kernel(const double *dots_part,
   }
   s = wave_sum(s);
   if (lane == 0) v[wave] = s;
+  if constexpr (WW) {
+    const double q = ww_sum_wave(ww_part, nww, threadIdx.x);
+    if (lane == 0) wwv[wave] = q;
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
     const double sse = hilo ? (double(hilo[0]) + double(hilo[1])) : v[3];
     scal[SC_TGG] = v[0];
     scal[SC_TGP] = v[1];
-    scal[SC_WW] = v[2];
     scal[SC_SSE] = sse;
     double loss = 0.5 * sse * inv_scale;
-    if (lambda != 0.0) loss += 0.5 * lambda * v[2];
+    if constexpr (WW) {
+      const double ww = ww_sum_fin(wwv);
+      scal[SC_WW] = ww;
+      loss = ww_loss(loss, lambda, ww);
+    } else {
+      scal[SC_WW] = v[2];
+      if (lambda != 0.0) loss += 0.5 * lambda * v[2];
+    }
     scal[SC_LOSS] = loss;
   }
 }
 
 void eval_tail(hipStream_t s, const double *dots_part, int nd, const double *sse_part, int nsse, const float *hilo,
-               double inv_scale, double lambda, double *scal, const int *abort) {
-  hipLaunchKernelGGL(eval_tail_kernel, dim3(1), dim3(256), 0, s, dots_part, nd, sse_part, nsse, hilo, inv_scale,
-                     lambda, scal, abort);
+               double inv_scale, double lambda, double *scal, const int *abort, WwPart ww) {
+  if (ww.part && lambda != 0.0)
+    hipLaunchKernelGGL(eval_tail_kernel<true>, dim3(1), dim3(256), 0, s, dots_part, nd, sse_part, nsse, hilo,
+                       inv_scale, lambda, scal, abort, ww.part, ww.n);
+  else
+    hipLaunchKernelGGL(eval_tail_kernel<false>, dim3(1), dim3(256), 0, s, dots_part, nd, sse_part, nsse, hilo,
+                       inv_scale, lambda, scal, abort, (const double *)nullptr, 0);
   LBF_KERNEL_CHECK();
 }
 

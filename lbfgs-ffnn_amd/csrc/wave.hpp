@@ -34,6 +34,23 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return lane_f64(v, 63);
 }
 
+// The one summation of a point's w.w partials (kernels.hpp WwPart). Threads 0..255 of the block take the words
+// r = t, t + 256, ..; each of waves 0..3 sums its lanes (wave_sum_f64); the caller stores wave w's value in
+// v[w] (w < 4), and after a barrier ww_sum_fin(v) = ((v0 + v1) + v2) + v3. Every consumer goes through these
+// two functions, so all of them form the same bits from the same words. Call with every thread of the block.
+__device__ __forceinline__ double ww_sum_wave(const double *part, int n, int t) {
+  double s = 0.0;
+  if (t < 256)
+    for (int r = t; r < n; r += 256) s += part[r];
+  return wave_sum_f64(s);
+}
+__device__ __forceinline__ double ww_sum_fin(const double *v) { return ((v[0] + v[1]) + v[2]) + v[3]; }
+// loss = data + 0.5 lambda w.w with the roundings fixed (one product, one fused multiply-add), whatever the
+// surrounding code is contracted to
+__device__ __forceinline__ double ww_loss(double data, double lambda, double ww) {
+  return __fma_rn(__dmul_rn(0.5, lambda), ww, data);
+}
+
 // Reductions over a DPP row (the 16 lanes l & ~15 .. l | 15): quad_perm [1,0,3,2] and [2,3,0,1], then
 // row_half_mirror and row_mirror. Each step combines a lane's value with its partner's, and both partners
 // form the same commutative pair, so all 16 lanes end with the same bits. Used by the softmax head, where

@@ -13,7 +13,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import (ACTS, INIT_CPU, INIT_CUDA, LOSSES, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED, SLBFGS_DP_SLICED,
+from ._lib import (ACTS, INIT_CPU, INIT_CUDA, LOSSES, check_l2, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED, SLBFGS_DP_SLICED,
                    GdParams, LbfError, LbfgsParams, Record, SgdParams, SlbfgsParams, SolveInfo, check, lib, ptr)
 
 
@@ -145,11 +145,13 @@ class Context:
 class Mlp:
     """Dense MLP; flat fp32 params in the reference layout [W (Out x In col-major) | b] per layer."""
 
-    def __init__(self, ctx: Context, dims: Sequence[int], acts: Sequence, loss: str = "mse"):
+    def __init__(self, ctx: Context, dims: Sequence[int], acts: Sequence, loss: str = "mse", l2: float = 0.0):
         """loss: "mse" (0.5 inv_scale ||net(X) - Y||^2, the reference's) or "softmax_xent" (softmax
-        cross-entropy on the logits of a linear last layer; lbf_mlp_set_loss)."""
+        cross-entropy on the logits of a linear last layer; lbf_mlp_set_loss). l2: weight decay of lbfgs_solve,
+        LbfgsRun, gd_solve and sgd_solve on this network (see the l2 property)."""
         if loss not in LOSSES:  # before anything touches the device
             raise LbfError(f"unknown loss {loss!r}: expected one of {sorted(LOSSES)}")
+        l2 = check_l2(l2)
         self.ctx = ctx
         self.dims = [int(d) for d in dims]
         self.acts = [ACTS[a] if isinstance(a, str) else int(a) for a in acts]
@@ -162,6 +164,21 @@ class Mlp:
         self.nparams = int(lib().lbf_mlp_param_count(h))
         if loss != "mse":
             self.loss_name = loss
+        if l2 != 0.0:
+            self.l2 = l2
+
+    @property
+    def l2(self) -> float:
+        """L2 weight decay (lbf_mlp_set_l2): lbfgs_solve, LbfgsRun, gd_solve and sgd_solve minimise and report
+        data loss + 0.5 l2 |w|^2. Read when a solve begins. Not used by loss_grad / hvp / fd_hvp / batch_grads
+        (their own l2 argument), slbfgs_solve (lam), loss() and lbfgs_solve_fn."""
+        v = C.c_double(-1.0)
+        check(lib().lbf_mlp_get_l2(self.h, C.byref(v)), "lbf_mlp_get_l2")
+        return v.value
+
+    @l2.setter
+    def l2(self, l2: float):
+        check(lib().lbf_mlp_set_l2(self.h, check_l2(l2)), "lbf_mlp_set_l2")
 
     @property
     def loss_name(self) -> str:

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import engine
-from ._lib import LOSSES, LbfError
+from ._lib import LOSSES, LbfError, check_l2
 
 
 @dataclass
@@ -48,6 +48,8 @@ class UnifiedConfig:
     write_csv: bool = True
     loss: str = "mse"            # "mse" or "softmax_xent" (HIP extension; train() applies a non-default choice
                                  # like UnifiedLauncher.setLoss, and it then stays the network's loss)
+    l2: float = 0.0              # weight decay of UnifiedLBFGS / UnifiedGD / UnifiedSGD (HIP extension; train()
+                                 # applies a non-zero value like UnifiedLauncher.setL2, and it then stays)
 
 
 @dataclass
@@ -109,6 +111,13 @@ class _DeviceNet:
         self.mlp: Optional[engine.Mlp] = None
         self.params: Optional[torch.Tensor] = None
         self.loss = "mse"
+        self.l2 = 0.0
+
+    def setL2(self, l2: float):
+        l2 = check_l2(l2)
+        if self.mlp is not None:
+            self.mlp.l2 = l2
+        self.l2 = l2
 
     def setLoss(self, loss: str):
         if loss not in LOSSES:
@@ -125,7 +134,7 @@ class _DeviceNet:
     def bindParams(self, seed: int = 123, mode: str = "cpu"):
         dims = [self.layers[0][0]] + [l[1] for l in self.layers]
         if self.mlp is None:
-            self.mlp = engine.Mlp(self.ctx, dims, [l[2] for l in self.layers], loss=self.loss)
+            self.mlp = engine.Mlp(self.ctx, dims, [l[2] for l in self.layers], loss=self.loss, l2=self.l2)
             self.params = self.mlp.new_params()
         self.mlp.init_params(seed, mode, self.params)
 
@@ -256,6 +265,12 @@ class UnifiedLauncher:
         cross-entropy on the logits; the last layer must be linear). Before or after buildNetwork()."""
         self.net_wrapper_.setLoss(loss)
 
+    def setL2(self, l2: float):
+        """L2 weight decay of UnifiedLBFGS, UnifiedGD and UnifiedSGD: they minimise and record
+        data loss + 0.5 l2 |w|^2 (UnifiedSLBFGS keeps its own lambda). evaluate() reports the data term only.
+        Before or after buildNetwork()."""
+        self.net_wrapper_.setL2(l2)
+
     def setData(self, data: UnifiedDataset):
         self.dataset_ = data
         self.data_ = _DeviceData(data, f"cuda:{self.ctx.device}", self.rank, self.world)
@@ -265,6 +280,8 @@ class UnifiedLauncher:
             print(f">>> Running HIP Experiment: {config.name}")
         if config.loss != "mse":
             self.setLoss(config.loss)
+        if check_l2(config.l2) != 0.0:
+            self.setL2(config.l2)
         if config.reset_params:
             self.net_wrapper_.bindParams(config.seed, config.init)
         recorder = optimizer.optimize(self.net_wrapper_, self.data_, config)
