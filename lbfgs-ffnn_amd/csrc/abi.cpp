@@ -167,7 +167,7 @@ int lbf_mlp_create(lbf_ctx *ctx, int nlayers, const int *dims, const int *acts, 
     auto *m = new lbf_mlp();
     m->ctx = ctx;
     try {
-      m->net.reset(new Mlp(&ctx->c, nlayers, dims, acts));
+      m->net.reset(new Mlp(&ctx->c, nlayers, dims, acts, read_switches()));
     } catch (...) {
       delete m;
       throw;
@@ -337,7 +337,7 @@ int lbf_two_loop(lbf_ctx *ctx, long long n, int k, const float *d_S, const float
     hipStream_t s = ctx->c.stream;
     const int policy = mode == 0 ? POL_CPU : (mode == 1 || mode == 3 ? POL_SLBFGS : POL_CUDA);
     const double dsign = mode == 1 || mode == 3 ? 1.0 : -1.0;
-    History h(&ctx->c, k, n);
+    History h(&ctx->c, k, n, read_switches().gram_fin);
     DevBuf<float> zero{size_t(n)};
     LBF_HIP(hipMemsetAsync(zero.get(), 0, size_t(n) * sizeof(float), s));
     if (mode == 3) { // the S-LBFGS solver's own route (SlbfgsSolver::epoch_steps)
@@ -518,7 +518,7 @@ int lbf_lbfgs_begin(lbf_mlp *net, const lbf_lbfgs_params *prm, float *d_params, 
     auto *s = new lbf_lbfgs();
     try {
       s->obj.reset(new MlpObjective(net->net.get(), d_X, d_Y, n_local, n_global));
-      s->s.reset(new LbfgsSolver(s->obj.get(), *prm, d_params));
+      s->s.reset(new LbfgsSolver(s->obj.get(), *prm, d_params, read_switches()));
     } catch (...) {
       delete s;
       throw;
@@ -567,7 +567,7 @@ int lbf_lbfgs_solve_fn(lbf_ctx *ctx, const lbf_lbfgs_params *prm, long long n, f
     LBF_REQUIRE(prm->m >= 0 && prm->m <= 128, "m in [0, 128]");
     ctx->c.set_device();
     CallbackObjective obj(&ctx->c, n, fn, user);
-    LbfgsSolver s(&obj, *prm, d_params);
+    LbfgsSolver s(&obj, *prm, d_params, read_switches());
     s.iterate(prm->max_iters, rec);
     s.info(info);
   });
@@ -605,7 +605,7 @@ int lbf_slbfgs_solve(lbf_mlp *net, const lbf_slbfgs_params *prm, float *d_params
   return guard([&] {
     LBF_REQUIRE(net && prm, "null argument");
     net->ctx->c.set_device();
-    SlbfgsSolver s(net->net.get(), *prm, d_params, d_X, d_Y, N);
+    SlbfgsSolver s(net->net.get(), *prm, d_params, d_X, d_Y, N, read_switches());
     s.run(rec);
     s.info(info);
   });
@@ -622,7 +622,7 @@ int lbf_slbfgs_begin(lbf_mlp *net, const lbf_slbfgs_params *prm, float *d_params
     net->ctx->c.set_device();
     auto *h = new lbf_slbfgs();
     try {
-      h->s.reset(new SlbfgsSolver(net->net.get(), *prm, d_params, d_X, d_Y, N));
+      h->s.reset(new SlbfgsSolver(net->net.get(), *prm, d_params, d_X, d_Y, N, read_switches()));
     } catch (...) {
       delete h;
       throw;

@@ -21,8 +21,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 namespace lbf {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -988,155 +986,6 @@ __global__ __launch_bounds__(256 * KW, KW == 1 ? 2 : 1) void gemm_glds_group_ker
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Wave-split-K direct-load main loop for the 32 x 128 tile (round 5; microbenchmark profiles/micro/loop32.hip,
-// whose results were lost with the session that ran it; library A/B in profiles/r05/g/, n/). The LDS-DMA loop of this tile spends ~1.8k cycles per 32-deep k-tile against 1024 of MFMA
-// issue: its DMA writes and fragment reads contend for the LDS while each wave waits on its reads, and the
-// DMA pieces' issue cost sits in front of the MFMAs. Here no operand is shared between waves and nothing
-// goes through LDS until the end: the four waves split every 32-deep k-tile (wave w: k 8w .. 8w+7, lane half
-// h: the 4 consecutive k 8w+4h .. +3), each lane loads its A quad A[row][k..k+3] and, per k, one 16-B quad of
-// the B row (columns n0 + 4 li .. +3) straight into registers, WSK_PD k-tiles ahead. The quad's 4 columns feed
-// 4 accumulators (accumulator c holds columns n0 + 4 j + c), 16 v_mfma_f32_32x32x2_f32 per wave per k-tile on 4
-// independent chains. After the loop the four waves' partial tiles are summed in wave order through LDS into
-// the standard accumulator layout (wave w owns columns n0 + 32w .. +31), so the epilogues (bias + activation,
-// split-K slab, the fused output layer) are the LDS-DMA kernel's. Fixed order throughout: a re-evaluation is
-// bitwise identical. Requires K, lda, ldb, N, k_chunk % 4 == 0 and 16-B aligned A, B (wsk_ok).
-// ------------------------------------------------------------------------------------------------
-constexpr int WSK_PD = 3;
-constexpr int WSK_RED_F = 4 * 16 * 2 * 128; // four waves' partial tiles, [wave][r][h][128 columns]
-constexpr int WSK_MAX_ASPLITS = 8;          // A-from-slabs: splits summed per quad (gemm_wsk_ok)
-
-// BKC: B stored k-contiguous (B[n*ldb + k]: the dX GEMM's W^T): a lane loads, per column block c, the quad
-// B[n0 + 32c + li][k..k+3], and accumulator c holds the standard columns n0 + 32c + j. Else (B n-contiguous)
-// the lane loads, per k, the quad B[k][n0 + 4li .. +3], and accumulator c holds columns n0 + 4j + c.
-// ASUM: the A quad is act(sum over the previous layer's forward split-K slabs in split order + bias) (the
-// LDS-DMA kernel's prologue and fwd_reduce_act's arithmetic), and the workgroups of column tile 0 store it to
-// a_out for the backward phase.
-template <int EPI, bool GATHER, bool BKC, bool ASUM>
-__global__ __launch_bounds__(256, 1) void gemm_wsk_kernel(const GemmK g) {
-  constexpr int BM = 32, BN = 128;
-  constexpr int HEAD_F = headc::smem_floats_epi(BN, headc::TB);
-  constexpr int LDS_F = HEAD_F > WSK_RED_F ? HEAD_F : WSK_RED_F;
-  constexpr int NA = ASUM ? WSK_MAX_ASPLITS : 1; // A quads per k-tile
-  __shared__ __attribute__((aligned(16))) float lds[LDS_F];
-  if (g.early.sse_part ? gemm_early_exit(g, lds) : (g.abort && *g.abort)) return;
-  if (int(blockIdx.z) < g.side_planes) {
-    gemm_side_job(g, reinterpret_cast<double *>(lds));
-    return;
-  }
-  const int zsplit = int(blockIdx.z) - g.side_planes;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int li = lane & 31, lh = lane >> 5;
-  const int m0 = int(blockIdx.y) * BM, n0 = int(blockIdx.x) * BN;
-  const int kb = zsplit * g.k_chunk;
-  const int ke = min(g.K, kb + g.k_chunk);
-  headc::EpiPrefetch<BN, BM, 256> hpre;
-  if constexpr (epi_head(EPI)) {
-    hpre.load(g.head_P, g.N, g.head_out, g.bias, g.head_Y, g.head_idx, m0, g.M);
-    if (g.head_fold > 0) hpre.load_fold(g.A, g.lda, g.a_idx, g.head_fold_c0, g.head_fold, m0, g.M);
-  }
-  // rows past M and columns past N read row 0 / column n0 (finite data); the epilogues mask them
-  const int row = m0 + li;
-  const bool rok = row < g.M;
-  long long grow = rok ? row : 0;
-  if (GATHER && rok) grow = g.a_idx[row];
-  const int k4 = 8 * wave + 4 * lh;
-  const float *ap = (ASUM ? g.a_slab : g.A) + grow * g.lda + kb + k4;
-  const float *bp[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    if constexpr (BKC) {
-      const int n = n0 + 32 * c + li;
-      bp[c] = g.B + (long long)(n < g.N ? n : n0) * g.ldb + kb + k4;
-    } else {
-      const int col = n0 + 4 * li;
-      bp[c] = g.B + (long long)(kb + k4 + c) * g.ldb + (col < g.N ? col : n0); // c: the k within the quad
-    }
-  }
-  const int nk = kb < ke ? (ke - kb + 31) / 32 : 0;
-  f32x16 acc[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[c][r] = 0.0f;
-  f32x4 ra[WSK_PD][NA], rb[WSK_PD][4], rbias[WSK_PD];
-  bool okm[WSK_PD];
-  // k-tile tt into register slot `slot`: clamped and unconditional (a k quad is all in or all out of
-  // [kb, ke): k4, kb, ke are multiples of 4); the mask is applied at the use
-  auto load = [&](int tt, int slot) {
-    const bool ok = kb + tt * 32 + k4 < ke;
-    const long long ko = ok ? (long long)tt * 32 : 0;
-    okm[slot] = ok;
-    if constexpr (ASUM) {
-#pragma unroll
-      for (int u = 0; u < NA; ++u) // every split's quad (clamped split; masked in the sum)
-        ra[slot][u] = *reinterpret_cast<const f32x4 *>(ap + (long long)min(u, g.a_splits - 1) * g.a_slab_stride + ko);
-      rbias[slot] = *reinterpret_cast<const f32x4 *>(g.a_bias + kb + k4 + ko);
-    } else {
-      ra[slot][0] = *reinterpret_cast<const f32x4 *>(ap + ko);
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      rb[slot][c] = *reinterpret_cast<const f32x4 *>(bp[c] + (BKC ? ko : ko * g.ldb));
-  };
-#pragma unroll
-  for (int p = 0; p < WSK_PD; ++p) load(p, p);
-  for (int i0 = 0; i0 < nk; i0 += WSK_PD) {
-#pragma unroll
-    for (int p = 0; p < WSK_PD; ++p) {
-      const int i = i0 + p;
-      if (i < nk) { // wave-uniform
-        f32x4 a;
-        if constexpr (ASUM) {
-          f32x4 sum = ra[p][0];
-#pragma unroll
-          for (int u = 1; u < NA; ++u)
-            if (u < g.a_splits) sum += ra[p][u];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) a[e] = act_rt(g.a_act, sum[e] + rbias[p][e]);
-          if (okm[p] && rok && n0 == 0) // column tile 0 stores the activations (bitwise fwd_reduce_act's)
-            *reinterpret_cast<f32x4 *>(g.a_out + (long long)row * g.lda + kb + k4 + (long long)i * 32) = a;
-        } else {
-          a = ra[p][0];
-        }
-        if (!okm[p]) a = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-            acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q], BKC ? rb[p][c][q] : rb[p][q][c], acc[c], 0, 0, 0);
-      }
-      // the slot's next k-tile, issued after the MFMAs that read it (no register copy, so no wait for the new
-      // data in this iteration): WSK_PD - 1 k-tiles of MFMAs ahead of its use
-      __builtin_amdgcn_sched_barrier(0);
-      load(i + WSK_PD, p);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  // the partial tiles, summed in wave order, into the standard layout (wave w: columns 32w + j)
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    float *dst = &lds[((wave * 16 + r) * 2 + lh) * 128];
-    if constexpr (BKC) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) dst[32 * c + li] = acc[c][r];
-    } else {
-      *reinterpret_cast<f32x4 *>(dst + li * 4) = f32x4{acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
-    }
-  }
-  __syncthreads();
-  f32x16 out[1][1];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    float v = lds[((0 * 16 + r) * 2 + lh) * 128 + 32 * wave + li];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) v += lds[((w * 16 + r) * 2 + lh) * 128 + 32 * wave + li];
-    out[0][0][r] = v;
-  }
-  __syncthreads(); // the LDS is the epilogue's now
-  gemm_epilogue<1, 4, 1, 1, EPI, 1>(g, out, lds, hpre, zsplit, m0, n0, 0, wave, li, lh, 0);
-}
-
 namespace {
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -1170,14 +1019,10 @@ template <int BM, int BN> GemmK make_gemmk(const GemmDesc &d) {
   k.gx = int(gx);
   k.gy = int(gy);
   k.group_z = 0;
-  static const bool xcd_off = [] { // A/B switch: LBF_NO_XCD=1 keeps the default block placement
-    const char *e = std::getenv("LBF_NO_XCD");
-    return e && std::atoi(e) != 0;
-  }();
-  // dW GEMMs only (A = activations^T, mn-contiguous). The split-K FORWARD of a minibatch (config 4's
+  // XCD placement: dW GEMMs only (A = activations^T, mn-contiguous). The split-K FORWARD of a minibatch (config 4's
   // 256 x 784 -> 512, 32 x 128 tiles, 8 splits) measured slower with it: 12.3 -> 13.2-13.7 us per launch for
   // 10.2 -> 7.9 MB of traffic (every CU of an XCD then streams the same W chunk at once); profiles/r05/k/.
-  k.xcd_swz = !xcd_off && d.epi == EPI_STORE && d.splits > 1 && !d.a_kc;
+  k.xcd_swz = d.epi == EPI_STORE && d.splits > 1 && !d.a_kc;
   k.side_planes = (d.side_slab && d.side_count > 0) ? int(cdiv(cdiv(d.side_count, SIDE_COLS), gx * gy)) : 0;
   k.side_slab = d.side_slab;
   k.side_splits = d.side_splits;
@@ -1259,47 +1104,12 @@ void launch(hipStream_t s, const GemmDesc &d, const GemmDesc *d2 = nullptr) {
   }
 }
 
-// gemm_wsk_kernel's conditions: 16-B quads everywhere. Opt-in (LBF_WSK=1): in the library's GEMMs it measured
-// no faster than the LDS-DMA loop at the 8-rank shard's fused-head forward and 10 % slower on config 4's
-// minibatch GEMMs (profiles/r05/g/), although its main loop alone measured 28 % faster (profiles/micro/loop32.hip).
-static bool wsk_ok(const GemmDesc &d) {
-  static const bool off = [] {
-    const char *e = std::getenv("LBF_WSK");
-    return !(e && std::atoi(e) != 0);
-  }();
-  const int kc = d.splits > 1 ? d.k_chunk : d.K;
-  const bool base = !off && d.a_kc && d.K % 4 == 0 && d.lda % 4 == 0 && d.ldb % 4 == 0 && kc % 4 == 0 &&
-                    aligned16(d.A) && aligned16(d.B);
-  if (!base) return false;
-  if (d.a_slab) // A from the previous layer's slabs: forward operand layout, split-K store or plain forward
-    return !d.b_kc && !d.a_idx && (d.epi == EPI_STORE || d.epi == EPI_FWD) && d.N % 4 == 0 && d.a_splits >= 1 &&
-           d.a_splits <= WSK_MAX_ASPLITS && d.a_slab_stride % 4 == 0 && aligned16(d.a_slab) && aligned16(d.a_bias) &&
-           aligned16(d.a_out);
-  if (d.b_kc) return d.epi == EPI_DX; // dX: B = W^T stored k-contiguous
-  return d.N % 4 == 0 && (d.epi == EPI_FWD || d.epi == EPI_STORE || d.epi == EPI_HEAD);
-}
-
 template <bool AKC, bool BKC, int EPI> void dispatch_tile(hipStream_t s, const GemmDesc &d) {
   // LDS-DMA stages: as many tile buffers as fit two workgroups per CU (80 KB each); the register-staged
   // fallback (gathered mn-contiguous operands, odd shapes) keeps two k-tiles of loads in flight
   if (d.tile == TILE_32x128) {
-    if constexpr (AKC) {
-      if (wsk_ok(d)) { // the wave-split-K direct-load loop (gemm_wsk_kernel)
-        GemmK k = make_gemmk<32, 128>(d);
-        const dim3 grid(unsigned(k.gx), unsigned(k.gy), unsigned((d.splits > 1 ? d.splits : 1) + k.side_planes));
-        if (d.a_slab) {
-          if constexpr (!BKC && !epi_head(EPI) && EPI != EPI_DX)
-            hipLaunchKernelGGL((gemm_wsk_kernel<EPI, false, false, true>), grid, dim3(256), 0, s, k);
-        } else if (d.a_idx) {
-          hipLaunchKernelGGL((gemm_wsk_kernel<EPI, true, BKC, false>), grid, dim3(256), 0, s, k);
-        } else {
-          hipLaunchKernelGGL((gemm_wsk_kernel<EPI, false, BKC, false>), grid, dim3(256), 0, s, k);
-        }
-        return;
-      }
-    }
-    // 32 x 128 (20 KB per stage), one 8-wave workgroup (two k-groups) per CU: the LDS-DMA loop (A from the
-    // previous layer's slabs, dX, shapes the direct loop does not take)
+    // 32 x 128 (20 KB per stage), one 8-wave workgroup (two k-groups) per CU. A wave-split-K loop with direct
+    // (register) loads measured no faster here and 10 % slower on config 4's minibatch GEMMs (profiles/r05/g/)
     launch<1, 4, 1, 1, AKC, BKC, EPI, 2, 2, 4>(s, d);
   } else if (d.tile == TILE_64x128) { // 64 x 128 (24 KB per stage), two workgroups per CU
     launch<2, 2, 1, 2, AKC, BKC, EPI, 1, 2, 3>(s, d);

@@ -87,10 +87,37 @@ private:
 };
 
 inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
-// Integer tuning knob from the environment (read once by the caller's static).
 inline int env_int(const char *name, int dflt) {
   const char *e = std::getenv(name);
   return e ? std::atoi(e) : dflt;
+}
+
+// The library's LBF_* route switches and diagnostics (INTEGRATION.md lists them). Whoever constructs an Mlp, a
+// History or a solver reads them then (the tests set a variable, then build a new object); nothing reads the
+// environment after construction. Unset means the default; any other text follows atoi.
+struct Switches {
+  int spec_depth = 3;      // LBF_SPEC_DEPTH: speculative line-search depth, 0 = host-driven (the solver clamps to 0..16)
+  bool fused_tail = true;  // LBF_FUSED_TAIL=0: the unfused history path
+  bool early = true;       // LBF_NO_EARLY=1: a speculative trial's Armijo test left to the fused tail
+  bool fold = true;        // LBF_NO_FOLD=1: the unfolded last dW rows
+  bool group_dw = true;    // LBF_NO_GROUP=1: dW of layers 1 and 0 in separate launches
+  int gram_fin = -1;       // LBF_GRAM_FIN=1 / 0 forces the history route, -1: by history length
+  bool full_ahead = false; // LBF_FULL_AHEAD=1: S-LBFGS's epoch-end full-batch evaluation on a third stream
+  int host_timing = 0;     // LBF_HOST_TIMING=1 / 2: host-side timing reports on stderr
+  bool show_plan = false;  // LBF_SHOW_PLAN=1: the tile and split plan on stderr
+};
+inline Switches read_switches() {
+  Switches w;
+  w.spec_depth = env_int("LBF_SPEC_DEPTH", w.spec_depth);
+  w.fused_tail = env_int("LBF_FUSED_TAIL", 1) != 0;
+  w.early = env_int("LBF_NO_EARLY", 0) == 0;
+  w.fold = env_int("LBF_NO_FOLD", 0) == 0;
+  w.group_dw = env_int("LBF_NO_GROUP", 0) == 0;
+  w.gram_fin = env_int("LBF_GRAM_FIN", w.gram_fin);
+  w.full_ahead = env_int("LBF_FULL_AHEAD", 0) != 0;
+  w.host_timing = env_int("LBF_HOST_TIMING", 0);
+  w.show_plan = env_int("LBF_SHOW_PLAN", 0) != 0;
+  return w;
 }
 
 // Extra flags for the library's events: every event orders work on ONE device (profiling marks, the

@@ -81,7 +81,8 @@ void Ctx::allreduce(float *buf, size_t count) {
 // ------------------------------------------------------------------------------------------------
 // Mlp
 // ------------------------------------------------------------------------------------------------
-Mlp::Mlp(Ctx *ctx, int nl, const int *dims, const int *acts) : ctx_(ctx) {
+Mlp::Mlp(Ctx *ctx, int nl, const int *dims, const int *acts, const Switches &sw)
+    : ctx_(ctx), group_dw_(sw.group_dw), fold_on_(sw.fold), show_plan_(sw.show_plan) {
   LBF_REQUIRE(nl >= 1 && nl <= 16, "1..16 layers");
   size_t off = 0;
   for (int l = 0; l < nl; ++l) {
@@ -96,8 +97,6 @@ Mlp::Mlp(Ctx *ctx, int nl, const int *dims, const int *acts) : ctx_(ctx) {
     layers_.push_back(L);
   }
   nparams_ = off;
-  if (const char *e = std::getenv("LBF_NO_FOLD")) fold_on_ = e[0] != '1'; // tests: the unfolded route
-  if (const char *e = std::getenv("LBF_NO_GROUP")) group_dw_ = e[0] != '1';
 }
 
 // Split-K factor for `tiles` output tiles over a K of `K` rows: the GEMM tiles run two workgroups per
@@ -176,8 +175,6 @@ void Mlp::plan(long long B) {
       if (2 * tiles32 <= cus) {
         L.ftile = TILE_32x128;
         fs = std::max(2LL, std::min(cus / tiles32, cdiv(L.in, 64))); // splits of >= 2 k-tiles
-        static const int fs_cap = env_int("LBF_FSPLIT_CAP", 0); // A/B of the split count (slab bytes vs depth)
-        if (fs_cap > 0) fs = std::min<long long>(fs, fs_cap);
       } else {
         fs = std::min(cdiv(384, ftiles), (long long)L.in / 128);
       }
@@ -240,8 +237,7 @@ void Mlp::plan(long long B) {
     L.slab_off = slab;
     if (L.splits > 1) slab += size_t(L.splits) * size_t(L.in + 1) * L.out; // every layer keeps its own slabs
   }
-  static const int show = env_int("LBF_SHOW_PLAN", 0);
-  if (show) {
+  if (show_plan_) {
     for (int l = 0; l < nl; ++l)
       std::fprintf(stderr, "[lbf plan] B=%lld layer %d: dW tile %d splits %d k_chunk %d | fwd tile %d splits %d\n", B,
                    l, layers_[l].dtile, layers_[l].splits, layers_[l].k_chunk, layers_[l].ftile, layers_[l].fsplits);
@@ -673,13 +669,13 @@ void Mlp::backward_phase(const float *P, float *G, const float *X, const int *id
     x.tile = dx_tile(B, L.in);
     return x;
   };
-  // A speculative first trial (tf->early: single rank; lambda != 0 with the point's w.w partials) takes its Armijo test in the first backward
-  // launch (EarlyLs, gemm.hip gemm_early_exit): on a failure that launch, the rest of the backward and the tail
-  // exit at entry, and the host finishes the search as after the tail's own rejection (LBF_NO_EARLY=1: off).
-  const bool early_on = env_int("LBF_NO_EARLY", 0) == 0; // read per evaluation: tests switch it in-process
+  // A speculative first trial (tf->early, set by the solver: single rank, Switches::early; lambda != 0 with the
+  // point's w.w partials) takes its Armijo test in the first backward launch (EarlyLs, gemm.hip gemm_early_exit):
+  // on a failure that launch, the rest of the backward and the tail exit at entry, and the host finishes the
+  // search as after the tail's own rejection.
   EarlyLs early;
   const EarlyLs *early_p = nullptr;
-  if (early_on && tf && tf->early && !reduced && (lambda == 0.0 || ww.part) && nloss > 0) {
+  if (tf && tf->early && !reduced && (lambda == 0.0 || ww.part) && nloss > 0) {
     early.sse_part = loss_part_.get();
     early.nsse = nloss;
     early.inv_scale = inv_scale;
@@ -1110,7 +1106,7 @@ void Mlp::hvp(const float *P, const float *V, const float *X, const float *Y, co
 // ------------------------------------------------------------------------------------------------
 // History
 // ------------------------------------------------------------------------------------------------
-History::History(Ctx *ctx, int m, long long n) : ctx_(ctx) {
+History::History(Ctx *ctx, int m, long long n, int gram_fin) : ctx_(ctx) {
   LBF_REQUIRE(m >= 0 && m <= 128, "history size m must be in [0, 128]");
   const int slots = m + 1;
   // Slot stride n rounded to 4 floats. (Rounded up to 2 MiB, the many-stream reads of the old combine pattern went
@@ -1165,9 +1161,8 @@ History::History(Ctx *ctx, int m, long long n) : ctx_(ctx) {
   }
   // Column sums + last-block step (gram_fin) for short histories; for m > 20 the fold_rows + hist_step route, which
   // measured faster there (two-loop at n = 10.49M: m = 10 58.0 against 57.5 %, m = 50 67.7 against 68.1 %,
-  // profiles/r06/j/). LBF_GRAM_FIN=1 / 0 forces either route (tests compare them).
-  const int gf = env_int("LBF_GRAM_FIN", -1);
-  gfin_on_ = gram_fin_supported(m) && (gf == 1 || (gf < 0 && m <= 20));
+  // profiles/r06/j/). gram_fin = 1 / 0 (LBF_GRAM_FIN) forces either route (tests compare them).
+  gfin_on_ = gram_fin_supported(m) && (gram_fin == 1 || (gram_fin < 0 && m <= 20));
   if (gfin_on_) {
     gdots_.resize(size_t(gram_ncols(m)));
     gcount_.resize(1);

@@ -113,7 +113,7 @@ struct ProfScope {
 // Dense MLP (the reference's CudaNetwork, src/cuda/network.cuh:21-158) with a cached workspace.
 class Mlp {
 public:
-  Mlp(Ctx *ctx, int nl, const int *dims, const int *acts);
+  Mlp(Ctx *ctx, int nl, const int *dims, const int *acts, const Switches &sw);
   size_t nparams() const { return nparams_; }
   const std::vector<Layer> &layers() const { return layers_; }
   Ctx *ctx() const { return ctx_; }
@@ -218,8 +218,9 @@ private:
   std::vector<DevBuf<float>> A_, D_;
   DevBuf<float> slab_, head_slab_, fslab_, fslab2_;
   float *fslab_buf(size_t l) const { return (l & 1) ? fslab2_.get() : fslab_.get(); } // forward slabs of layer l
-  bool group_dw_ = true;      // dW of layers 1 and 0 in one launch (LBF_NO_GROUP=1: separate launches)
-  bool fold_on_ = true;       // fold into the EPI_HEAD epilogue (LBF_NO_FOLD=1: the unfolded route, tests)
+  const bool group_dw_;  // dW of layers 1 and 0 in one launch (Switches::group_dw)
+  const bool fold_on_;   // fold into the EPI_HEAD epilogue (Switches::fold; off: the unfolded route, tests)
+  const bool show_plan_; // plan() reports each plan on stderr
   bool rowhead_on(long long B) const; // the standalone head fed by the last hidden layer's slabs
   // Planned fold: the last hidden layer's [dW ; db] rows fold_c0_ .. in (fold_ input columns and the
   // bias row) are computed in the forward GEMM's EPI_HEAD epilogue instead of a mostly empty last
@@ -243,7 +244,8 @@ constexpr int kGramFold = 32;
 
 class History {
 public:
-  History(Ctx *ctx, int m, long long n);
+  // gram_fin: Switches::gram_fin (1 / 0 forces the history route, -1: by history length)
+  History(Ctx *ctx, int m, long long n, int gram_fin);
   HistView view() const { return v_; }
   void reset();
   // Gram sweep + bookkeeping (+ direction coefficients when want_dir > 0).

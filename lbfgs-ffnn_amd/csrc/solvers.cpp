@@ -31,9 +31,9 @@ void CallbackObjective::eval(const float *x, float *g, const float *pdir, double
   LBF_HIP(hipMemcpyAsync(scal + SC_LOSS, hl.get(), sizeof(double), hipMemcpyHostToDevice, c->stream));
 }
 
-LbfgsSolver::LbfgsSolver(Objective *obj, const lbf_lbfgs_params &prm, float *d_params)
-    : obj_(obj), ctx_(obj->ctx()), prm_(prm), user_params_(d_params), n_(obj->n()),
-      hist_(obj->ctx(), prm.m, obj->n()) {
+LbfgsSolver::LbfgsSolver(Objective *obj, const lbf_lbfgs_params &prm, float *d_params, const Switches &sw)
+    : early_(sw.early), host_timing_(sw.host_timing), obj_(obj), ctx_(obj->ctx()), prm_(prm), user_params_(d_params),
+      n_(obj->n()), hist_(obj->ctx(), prm.m, obj->n(), sw.gram_fin) {
   LBF_REQUIRE(d_params, "null pointer");
   LBF_REQUIRE(prm.max_line_iters >= 1, "max_line_iters >= 1");
   for (int i = 0; i < 3; ++i) {
@@ -50,14 +50,12 @@ LbfgsSolver::LbfgsSolver(Objective *obj, const lbf_lbfgs_params &prm, float *d_p
   hs_.ensure(SC_N);
   // Speculation depth: iterations enqueued ahead of the host's line-search decision
   // (LBF_SPEC_DEPTH, default 3; 0 = host-driven). Host callbacks synchronise anyway.
-  depth_ = 3;
-  if (const char *e = std::getenv("LBF_SPEC_DEPTH")) depth_ = std::max(0, std::min(16, std::atoi(e)));
-  if (!obj_->async()) depth_ = 0;
+  depth_ = obj_->async() ? std::max(0, std::min(16, sw.spec_depth)) : 0;
   // Fused optimizer tail on the speculative path (LBF_FUSED_TAIL=0 disables). It is a latency design
   // (one block per 64 coordinates, a partial row each): past kFusedTailMaxN the classic Gram sweep +
   // folded history step moves fewer bytes.
-  fuse_ = depth_ > 0 && obj_->fused_tail() && prm_.m > 0 && prm_.m <= TAIL_MAXM && n_ <= kFusedTailMaxN;
-  if (const char *e = std::getenv("LBF_FUSED_TAIL")) fuse_ = fuse_ && e[0] != '0';
+  fuse_ = sw.fused_tail && depth_ > 0 && obj_->fused_tail() && prm_.m > 0 && prm_.m <= TAIL_MAXM &&
+          n_ <= kFusedTailMaxN;
   if (depth_ > 0) {
     abort_.resize(1);
     LBF_HIP(hipMemsetAsync(abort_.get(), 0, sizeof(int), ctx_->stream));
@@ -194,7 +192,7 @@ float LbfgsSolver::begin_iteration(const LsCtlArgs *ls) {
     tf.iter_next = iter_ + 1;
     tf.ls = *ls;
     tf.ls.alphaf = alpha;
-    tf.early = ls->first ? 0 : 1; // (Wolfe iteration 0 takes its trial without a test)
+    tf.early = (early_ && !ls->first) ? 1 : 0; // (Wolfe iteration 0 takes its trial without a test)
     obj_->eval_fused(xt_, gt_, p_.get(), hist_.scal(), tf);
     return alpha;
   }
@@ -228,7 +226,7 @@ float LbfgsSolver::begin_iteration(const LsCtlArgs *ls) {
     tf.iter_next = iter_ + 1;
     tf.ls = *ls;
     tf.ls.alphaf = alpha;
-    tf.early = ls->first ? 0 : 1; // (Wolfe iteration 0 takes its trial without a test)
+    tf.early = (early_ && !ls->first) ? 1 : 0; // (Wolfe iteration 0 takes its trial without a test)
     announce_ww(xt_);
     obj_->eval_fused(xt_, gt_, p_.get(), hist_.scal(), tf);
   } else {
@@ -508,7 +506,6 @@ int LbfgsSolver::iterate_spec(int iters, lbf_record *rec) {
     ~Clear() { c->abort = nullptr; }
   } clear{ctx_};
   // LBF_HOST_TIMING=1: where the host thread spends an iteration (enqueue vs waiting for the device)
-  static const int host_timing = env_int("LBF_HOST_TIMING", 0);
   double t_enq = 0.0, t_wait = 0.0;
   long long n_wait = 0, n_ready = 0;
   using clk = std::chrono::steady_clock;
@@ -554,12 +551,12 @@ int LbfgsSolver::iterate_spec(int iters, lbf_record *rec) {
     q.pop_front();
     SpecRecord r;
     const auto tw0 = clk::now();
-    if (host_timing) {
+    if (host_timing_) {
       t_enq += std::chrono::duration<double>(tw0 - te0).count();
       n_ready += __atomic_load_n(&spec_rec_[f.seq % kSpecRing].seq, __ATOMIC_ACQUIRE) == f.seq ? 1 : 0;
     }
     wait_record(f.seq, &r);
-    if (host_timing) {
+    if (host_timing_) {
       t_wait += std::chrono::duration<double>(clk::now() - tw0).count();
       ++n_wait;
     }
@@ -597,7 +594,7 @@ int LbfgsSolver::iterate_spec(int iters, lbf_record *rec) {
       host_fold = true;
     }
   }
-  if (host_timing && n_wait)
+  if (host_timing_ && n_wait)
     std::fprintf(stderr, "[lbf host] spec: %lld records, enqueue %.2f us/iter, wait %.2f us/iter, %lld already there\n",
                  n_wait, 1e6 * t_enq / double(n_wait), 1e6 * t_wait / double(n_wait), n_ready);
   return done;
@@ -630,9 +627,9 @@ void fd_hvp_grads(Mlp *net, const float *u, const float *s, const float *X, cons
 }
 
 SlbfgsSolver::SlbfgsSolver(Mlp *net, const lbf_slbfgs_params &prm, float *d_params, const float *X, const float *Y,
-                           long long N)
-    : net_(net), ctx_(net->ctx()), prm_(prm), user_params_(d_params), X_(X), Y_(Y), N_(N),
-      n_((long long)net->nparams()), hist_(net->ctx(), prm.M, (long long)net->nparams()) {
+                           long long N, const Switches &sw)
+    : host_timing_(sw.host_timing), net_(net), ctx_(net->ctx()), prm_(prm), user_params_(d_params), X_(X), Y_(Y),
+      N_(N), n_((long long)net->nparams()), hist_(net->ctx(), prm.M, (long long)net->nparams(), sw.gram_fin) {
   LBF_REQUIRE(d_params && X && Y && N > 0, "null pointer / empty data");
   LBF_REQUIRE(prm.b > 0 && prm.L > 0 && prm.L + 1 <= 64, "b > 0, 1 <= L <= 63");
   const size_t nv = size_t(round4(n_)), ng = size_t(round4(n_ + 2));
@@ -686,7 +683,7 @@ SlbfgsSolver::SlbfgsSolver(Mlp *net, const lbf_slbfgs_params &prm, float *d_para
       acts.push_back(L.act);
     }
     dims.push_back(net->layers().back().out);
-    tnet_.reset(new Mlp(tctx_.get(), int(acts.size()), dims.data(), acts.data()));
+    tnet_.reset(new Mlp(tctx_.get(), int(acts.size()), dims.data(), acts.data(), sw));
     tnet_->set_loss(net->loss()); // the twins evaluate the caller's objective
     LBF_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming | event_release_flags()));
     LBF_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming | event_release_flags()));
@@ -697,7 +694,7 @@ SlbfgsSolver::SlbfgsSolver(Mlp *net, const lbf_slbfgs_params &prm, float *d_para
     const int dev = ctx_->device;
     tw_.reset(new TaskFifo([dev]() { LBF_HIP(hipSetDevice(dev)); }));
     // the epoch-end full-batch evaluation ahead (see fnet_): single rank, opt-in (LBF_FULL_AHEAD=1)
-    if (!ctx_->dp() && env_int("LBF_FULL_AHEAD", 0) != 0) {
+    if (!ctx_->dp() && sw.full_ahead) {
       fctx_.reset(new Ctx());
       fctx_->device = ctx_->device;
       fctx_->cus = ctx_->cus;
@@ -707,7 +704,7 @@ SlbfgsSolver::SlbfgsSolver(Mlp *net, const lbf_slbfgs_params &prm, float *d_para
       fctx_->prof.on = ctx_->prof.on;
       fctx_->prof.only = ctx_->prof.only;
       fctx_->prof.every = ctx_->prof.every;
-      fnet_.reset(new Mlp(fctx_.get(), int(acts.size()), dims.data(), acts.data()));
+      fnet_.reset(new Mlp(fctx_.get(), int(acts.size()), dims.data(), acts.data(), sw));
       fnet_->set_loss(net->loss());
       mu_next_.resize(ng);
       fscal_.resize(SC_N);
@@ -957,12 +954,11 @@ void SlbfgsSolver::epoch_steps(const EpochDraw &d) {
   };
   // LBF_HOST_TIMING=2: host time of each part of the inner step's enqueue (where the epoch's host-bound
   // ~130 us per step go)
-  static const int host_timing = env_int("LBF_HOST_TIMING", 0);
   using hclk = std::chrono::steady_clock;
   double ht[6] = {0, 0, 0, 0, 0, 0}; // twin, main eval, events, direction, combine, Hessian step
-  auto tick = [&]() { return host_timing >= 2 ? hclk::now() : hclk::time_point(); };
+  auto tick = [&]() { return host_timing_ >= 2 ? hclk::now() : hclk::time_point(); };
   auto tock = [&](int i, hclk::time_point a) {
-    if (host_timing >= 2) ht[i] += std::chrono::duration<double, std::micro>(hclk::now() - a).count();
+    if (host_timing_ >= 2) ht[i] += std::chrono::duration<double, std::micro>(hclk::now() - a).count();
   };
   if (!twin_free) {
     // the twin may reuse block t & 1 once the direction of step t - 2 has read it: nothing of this epoch
@@ -1069,7 +1065,7 @@ void SlbfgsSolver::epoch_steps(const EpochDraw &d) {
     tock(5, h0);
   }
   if (tw_) tw_->wait_all(); // every twin task of the epoch enqueued
-  if (host_timing >= 2)
+  if (host_timing_ >= 2)
     std::fprintf(stderr, "[lbf host] per inner step (us): twin %.1f, main eval %.1f, events %.1f, direction %.1f, "
                  "combine %.1f, Hessian step %.1f\n", ht[0] / m_inner, ht[1] / m_inner, ht[2] / m_inner,
                  ht[3] / m_inner, ht[4] / m_inner, ht[5] / m_inner);
@@ -1142,14 +1138,13 @@ int SlbfgsSolver::iterate(int epochs, lbf_record *rec) {
     // twin through the event it waits on at the epoch's start), so the host enqueues the first inner step
     // while the gathers run.
     // --- epoch -----------------------------------------------------------------------------------
-    static const int host_timing = env_int("LBF_HOST_TIMING", 0);
     const auto th0 = std::chrono::steady_clock::now();
     {
       // replicated data parallelism: the inner steps evaluate without the communicator
       LocalOnly lo_guard(ctx_, repl_);
       epoch_steps(cur_);
     }
-    if (host_timing) { // host time to enqueue the epoch's inner steps vs the epoch on the device
+    if (host_timing_) { // host time to enqueue the epoch's inner steps vs the epoch on the device
       const auto th1 = std::chrono::steady_clock::now();
       LBF_HIP(hipStreamSynchronize(s));
       const auto th2 = std::chrono::steady_clock::now();

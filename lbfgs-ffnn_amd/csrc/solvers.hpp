@@ -119,7 +119,8 @@ struct CallbackObjective : Objective {
 // the host only reads a 16-double status block once per line-search trial.
 class LbfgsSolver {
 public:
-  LbfgsSolver(Objective *obj, const lbf_lbfgs_params &prm, float *d_params);
+  // sw: speculation depth, fused tail, early Armijo test, host timing; the history's route
+  LbfgsSolver(Objective *obj, const lbf_lbfgs_params &prm, float *d_params, const Switches &sw);
   ~LbfgsSolver();
   // Runs up to `iters` iterations. Returns the number run (fewer on convergence).
   int iterate(int iters, lbf_record *rec);
@@ -168,6 +169,8 @@ private:
   int depth_ = 0;
   int seq_ = 0;
   bool fuse_ = false;      // fused optimizer tail on the speculative path
+  const bool early_;       // a speculative first trial's Armijo test in its first backward launch (Switches::early)
+  const int host_timing_;  // Switches::host_timing
   bool dir_ready_ = false; // the last fused tail left the next direction's coefficients on the device
   DevBuf<int> abort_;
   SpecRecord *spec_rec_ = nullptr;
@@ -200,8 +203,9 @@ private:
 
 class SlbfgsSolver {
 public:
+  // sw: full-ahead, host timing; the history's route and the switches of the twin workspaces' Mlps
   SlbfgsSolver(Mlp *net, const lbf_slbfgs_params &prm, float *d_params, const float *X, const float *Y,
-               long long N);
+               long long N, const Switches &sw);
   ~SlbfgsSolver();
   int run(lbf_record *rec);                 // prm.max_epochs epochs (lbf_slbfgs_solve)
   int iterate(int epochs, lbf_record *rec); // up to `epochs` more (lbf_slbfgs_begin / iterate / end)
@@ -219,6 +223,7 @@ public:
   }
 
 private:
+  const int host_timing_; // Switches::host_timing
   int pio_cap_ = 0, nev_ = 0;
   float *pio_rec_ = nullptr;
   const float *pio_force_ = nullptr;

@@ -954,38 +954,16 @@ static constexpr int GRAM_THREADS = 512;
 static long long gram_max_chunk() { return 4096; }
 
 int gram_ncols(int m) { return 6 * m + 6; }
-template <int U, bool NT, int MODE = 0>
-__global__ __launch_bounds__(GRAM_THREADS) void gram_kernel(const GramArgs a, long long chunk, double *partials, int tr,
-                                                            int vec);
-// Workgroups of the Gram sweep resident on the whole chip at the largest chunk (LDS-bound: 3 per CU), once.
-static long long gram_slots() {
-  static const long long slots = [] {
-    int dev = 0, cus = 0, per = 0;
-    LBF_HIP(hipGetDevice(&dev));
-    LBF_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    LBF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, gram_kernel<4, true>, GRAM_THREADS,
-                                                         size_t(3 * gram_max_chunk()) * sizeof(float)));
-    return (long long)std::max(1, cus) * std::max(1, per);
-  }();
-  return slots;
-}
 int gram_nwg(long long n) {
   long long w = cdiv(n, 1024);
   if (w > 2048) w = 2048;
-  long long need = cdiv(n, gram_max_chunk());
+  // More chunks than the chip holds workgroups at once (n = 10.49M: 2561 chunks, 3.33 rounds of 768): rounding the
+  // count up to whole rounds measured no faster, 5.35-5.41 against 5.44-5.47 TB/s, profiles/r06/h/
+  const long long need = cdiv(n, gram_max_chunk());
   if (w < need) w = need;
-  // More workgroups than the chip holds at once: a whole number of rounds, every round full (n = 10.49M:
-  // 2561 chunks of 4096 were 3.33 rounds of 768 resident workgroups, the last a third full; now 3072 of
-  // 3416), chunks still <= 4096.
-  const long long slots = gram_slots();
-  // (whole rounds of workgroups measured no faster than 4096-element chunks, 5.35-5.41 against 5.44-5.47 TB/s at
-  // n = 10.49M, profiles/r06/h/; LBF_GRAM_ROUNDS=1 for the A/B)
-  static const int whole_rounds = env_int("LBF_GRAM_ROUNDS", 0);
-  if (whole_rounds && w > slots) w = cdiv(need, slots) * slots;
   return int(w < 1 ? 1 : w);
 }
 static long long gram_chunk(long long n, int nwg) { return cdiv(cdiv(n, nwg), 4) * 4; }
-
 
 // The new vectors of one element: gram_kernel's arithmetic (s = sa - sb, y = (ya - yb) * yscale into the
 // ring's write slot, g = ga - gb + gc into g_out), staged in LDS, self dots accumulated.
@@ -1016,7 +994,7 @@ __device__ __forceinline__ GramNew gram_new(const GramArgs &a, float sa, float s
 // MODE 2 then stages s, y, g of its chunk from memory into LDS and runs the history phase. The fused form's
 // phase-1 stores, made between the history streams, cost the sweep far more than their bytes (5.2-5.7 TB/s
 // against 5.8-6.0 split, profiles/micro/ring_ld.hip gram3p_*, profiles/r06/k2/).
-template <int U, bool NT, int MODE>
+template <int U, bool NT, int MODE = 0>
 __global__ __launch_bounds__(GRAM_THREADS) void gram_kernel(const GramArgs a, long long chunk, double *partials, int tr,
                                                             int vec) {
   if (a.h.abort && *a.h.abort) return;
@@ -1219,10 +1197,9 @@ void gram_update(hipStream_t s, const GramArgs &a, double *partials, int transpo
                   al16(a.g_out);
   const int tr = transposed ? 1 : 0;
   // the split sweep (MODE 1 then 2) for the large-n history, where g is readable afterwards (ga, or g_out when formed)
-  static const int split_on = env_int("LBF_GRAM_SPLIT", 1); // A/B: 0 keeps the fused sweep
   // (long histories only: at m = 10 the extra launch and the three staged reads cost what the split saves, two-loop
   // 56.9-57.5 % split against 57.1-58.1 % fused; m = 50 68.9-69.6 % against 67.2-67.3 %, profiles/r06/m/)
-  if (split_on && vec && a.h.n >= (1LL << 21) && a.h.m >= 20 && !(a.has_g && (a.gb || a.gc) && !a.g_out)) {
+  if (vec && a.h.n >= (1LL << 21) && a.h.m >= 20 && !(a.has_g && (a.gb || a.gc) && !a.g_out)) {
     const dim3 g1{unsigned(nwg), 1, 1}, b1{unsigned(GRAM_THREADS), 1, 1};
     if (nt) {
       hipLaunchKernelGGL((gram_kernel<4, true, 1>), g1, b1, 0, s, a, chunk, partials, tr, vec);
@@ -1420,85 +1397,14 @@ void hist_coef(hipStream_t s, const CoefArgs &a) {
 // History: linear-combination sweep  dir = sum_i cs_i S_i + cy_i Y_i + cg g  (fp64 per element),
 // fused with the trial point x_out = x_in + alpha*dir (and an optional second copy).
 // ---------------------------------------------------------------------------------------------
-template <int U, bool NT>
-__global__ __launch_bounds__(256) void combine_kernel(const CombineArgs a) {
-  if (a.h.abort && *a.h.abort) return;
-  __shared__ double cs[COEF_MAXK], cy[COEF_MAXK];
-  __shared__ int L[COEF_MAXK];
-  const HistView &h = a.h;
-  const int S_ = h.slots;
-  const int k = h.ist[IST_COUNT];
-  for (int i = threadIdx.x; i < k; i += blockDim.x) {
-    cs[i] = h.coef[i];
-    cy[i] = h.coef[S_ + i];
-    L[i] = h.ist[IST_ORDER + i];
-  }
-  __syncthreads();
-  const double cg = h.coef[2 * S_];
-  const double alpha = a.alpha_from_state ? h.scal[SC_ALPHA0] : a.alpha;
-  // grid-stride over 16-B quads: the grid is the chip's resident workgroups, so every one takes the same
-  // number of quads (within one) and there is no partly filled last round
-  const long long stride = (long long)gridDim.x * blockDim.x * 4;
-  for (long long e = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; e < h.n; e += stride) {
-  if (e + 3 < h.n) {
-    const f32x4 g4 = *reinterpret_cast<const f32x4 *>(a.g + e);
-    const f32x4 x4 = *reinterpret_cast<const f32x4 *>((a.x_out ? a.x_in : a.g) + e); // unconditional: no early wait
-    double acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = cg * double(g4[j]);
-    int i = 0;
-    for (; i + U <= k; i += U) { // 2U independent 16-B loads in flight per lane
-      f32x4 s4[U], y4[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        s4[u] = hist_load<NT>(h.S + (long long)L[i + u] * h.ld + e);
-        y4[u] = hist_load<NT>(h.Y + (long long)L[i + u] * h.ld + e);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] += cs[i + u] * double(s4[u][j]) + cy[i + u] * double(y4[u][j]);
-    }
-    for (; i < k; ++i) {
-      const f32x4 s4 = *reinterpret_cast<const f32x4 *>(h.S + (long long)L[i] * h.ld + e);
-      const f32x4 y4 = *reinterpret_cast<const f32x4 *>(h.Y + (long long)L[i] * h.ld + e);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] += cs[i] * double(s4[j]) + cy[i] * double(y4[j]);
-    }
-    f32x4 d4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) d4[j] = float(acc[j]);
-    if (a.dir) *reinterpret_cast<f32x4 *>(a.dir + e) = d4;
-    if (a.x_out) {
-      const f32x4 o4 = x4 + float(alpha) * d4;
-      *reinterpret_cast<f32x4 *>(a.x_out + e) = o4;
-      if (a.x_out2) *reinterpret_cast<f32x4 *>(a.x_out2 + e) = o4;
-    }
-  } else {
-    for (long long q = e; q < h.n; ++q) {
-      double acc = cg * double(a.g[q]);
-      for (int i = 0; i < k; ++i)
-        acc += cs[i] * double(h.S[(long long)L[i] * h.ld + q]) + cy[i] * double(h.Y[(long long)L[i] * h.ld + q]);
-      const float d = float(acc);
-      if (a.dir) a.dir[q] = d;
-      if (a.x_out) {
-        const float o = a.x_in[q] + float(alpha) * d;
-        a.x_out[q] = o;
-        if (a.x_out2) a.x_out2[q] = o;
-      }
-    }
-  }
-  }
-}
 
-// Large-n combine with the Gram sweep's access pattern (round 6). combine_kernel above reads, per wave-instruction,
-// 1 KB of one vector and per lane one quad of every live vector, the grid striding over the elements: the chip
-// then touches every vector at the same few offsets at once, a pattern that streams at 5.45 TB/s against 6.7 TB/s
-// for the Gram sweep's (each wave 4-16 KB contiguous of one vector; profiles/micro/ring_ld.hip, profiles/r06/d/).
+// Large-n combine with the Gram sweep's access pattern (round 6). A grid striding over the elements, one quad of
+// every live vector per lane (1 KB of one vector per wave-instruction), has the chip touch every vector at the
+// same few offsets at once, a pattern that streams at 5.45 TB/s against 6.7 TB/s for the Gram sweep's (each wave 4-16 KB contiguous of one vector; profiles/micro/ring_ld.hip, profiles/r06/d/, o/).
 // Here a workgroup owns 4096-element chunks (grid-stride over the resident grid): wave w the 1024 elements
 // c0 + 1024 w .., lane l the quads 256 u + 4 l (u < 4), so each vector is read as 4 KB contiguous per wave and
-// 16 KB per workgroup, V vectors' quads (2 V x 4 loads) in flight per lane. Per element the same fp64 sum in the
-// same order as combine_kernel (cg g, then cs_i S_i + cy_i Y_i for i = 0 .. k - 1).
+// 16 KB per workgroup, V vectors' quads (2 V x 4 loads) in flight per lane. Per element one fp64 sum in a fixed
+// order: cg g, then cs_i S_i + cy_i Y_i for i = 0 .. k - 1.
 template <int V, bool NT, int Q = 4>
 __global__ __launch_bounds__(256) void combine_chunk_kernel(const CombineArgs a) {
   if (a.h.abort && *a.h.abort) return;
@@ -1677,39 +1583,21 @@ void hist_combine(hipStream_t s, const CombineArgs &ca) {
 }
 
 static void combine_stream(hipStream_t s, const CombineArgs &a) {
-  static const int chunked = env_int("LBF_COMBINE_CHUNK", 1); // A/B: 0 keeps combine_kernel
-  if (chunked) {
-    // 2 vectors x 4 quads in flight per lane: measured against 1 x 4, 2 x 2 and 4 x 2 (m = 50: 69.9-70.0 % against
-    // 69.5-69.9, 67.3-67.6, 66.7-66.8 %; profiles/r06/o/)
-    static const long long res_c = [] { // workgroups of combine_chunk_kernel the chip holds at once, once
-      int dev = 0, cus = 0, p1 = 0, p2 = 0;
-      LBF_HIP(hipGetDevice(&dev));
-      LBF_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-      LBF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&p1, combine_chunk_kernel<2, true, 4>, 256, 0));
-      LBF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&p2, combine_chunk_kernel<2, false, 4>, 256, 0));
-      return (long long)std::max(1, cus) * std::max(1, std::min(p1, p2));
-    }();
-    const dim3 grid(unsigned(std::min(cdiv(a.h.n, 4096LL), res_c)));
-    if (hist_nt(a.h))
-      hipLaunchKernelGGL((combine_chunk_kernel<2, true, 4>), grid, dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL((combine_chunk_kernel<2, false, 4>), grid, dim3(256), 0, s, a);
-    LBF_KERNEL_CHECK();
-    return;
-  }
-  static const long long resident = [] { // workgroups of combine_kernel the chip holds at once, once
-    int dev = 0, cus = 0, p8 = 0, p4 = 0;
+  // 2 vectors x 4 quads in flight per lane: measured against 1 x 4, 2 x 2 and 4 x 2 (m = 50: 69.9-70.0 % against
+  // 69.5-69.9, 67.3-67.6, 66.7-66.8 %; profiles/r06/o/)
+  static const long long resident = [] { // workgroups of combine_chunk_kernel the chip holds at once, once
+    int dev = 0, cus = 0, p1 = 0, p2 = 0;
     LBF_HIP(hipGetDevice(&dev));
     LBF_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    LBF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&p8, combine_kernel<8, true>, 256, 0));
-    LBF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&p4, combine_kernel<4, false>, 256, 0));
-    return (long long)std::max(1, cus) * std::max(1, std::min(p8, p4));
+    LBF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&p1, combine_chunk_kernel<2, true>, 256, 0));
+    LBF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&p2, combine_chunk_kernel<2, false>, 256, 0));
+    return (long long)std::max(1, cus) * std::max(1, std::min(p1, p2));
   }();
-  const dim3 grid(unsigned(std::min(cdiv(cdiv(a.h.n, 4), 256), resident)));
+  const dim3 grid(unsigned(std::min(cdiv(a.h.n, 4096LL), resident)));
   if (hist_nt(a.h))
-    hipLaunchKernelGGL((combine_kernel<8, true>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((combine_chunk_kernel<2, true>), grid, dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL((combine_kernel<4, false>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((combine_chunk_kernel<2, false>), grid, dim3(256), 0, s, a);
   LBF_KERNEL_CHECK();
 }
 
