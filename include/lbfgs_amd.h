@@ -162,6 +162,40 @@ int lbf_mlp_get_loss(const lbf_mlp *net, int *loss);
  * lbf_mlp_loss (the data term) and lbf_lbfgs_solve_fn (the callback is the whole objective). */
 int lbf_mlp_set_l2(lbf_mlp *net, double l2);
 int lbf_mlp_get_l2(const lbf_mlp *net, double *l2);
+/* Device-side evaluation (extension; replaces the host scan of UnifiedLauncher::evaluate,
+ * src/unified_launcher.hpp:154-199, which copies every output to the host): forward pass and one metrics kernel
+ * per chunk of chunk_rows rows (0: 65536, or the batch if smaller; the activation workspace is bounded by the
+ * chunk, and no result depends on the chunking beyond the regrouping of the loss's fp64 sum).
+ *   predicted class of a row: the reference's scan: best = 0, m = -1e20; for o = 0..Out-1: if z_o > m take it.
+ *     The lowest index wins a tie, a NaN never wins, a row with nothing above -1e20 gives 0 (numpy.argmax differs
+ *     on NaN rows). z = what lbf_mlp_forward returns: the outputs of an MSE net, the logits of a cross-entropy net.
+ *   target class: the same scan over the target row (one-hot or soft); d_idx gathers target and input rows.
+ *   correct: rows with predicted == target class.
+ *   topk:    rows whose target class t has rank < k, rank = #{o : z_o > z_t} + #{o < t : z_o == z_t}, 1 <= k <= Out;
+ *            for finite outputs k = 1 gives correct. Rows holding a non-finite output are outside this contract;
+ *            they are counted in rows and never fault.
+ *   loss:    the network's data loss with the caller's inv_scale, as lbf_mlp_loss defines it (no l2 term),
+ *            accumulated in fp64 in a fixed order: a second call gives the bitwise same value.
+ *   h_confusion (nullable, needs d_Y): Out*Out counts, [target * Out + predicted].
+ *   d_pred (nullable): batch ints, the predicted class per row, in batch (gathered) order.
+ *   d_proba (nullable): batch*Out floats, softmax of the logits; LBF_LOSS_SOFTMAX_XENT nets only.
+ * d_Y NULL: predictions only; loss, correct and topk are 0. With a communicator every rank passes its own
+ * batch local rows (0 is legal: an empty share) and receives the totals over all ranks, bitwise the same on every
+ * rank (world <= 256); d_pred and d_proba stay local. Synchronous: it returns host values.
+ * LBF_ERR_INVALID: null handles, k outside 1..Out, h_confusion without d_Y, d_proba on an MSE net.
+ * All state is the network's own: no other network's evaluation and no solver of another network is disturbed.
+ * To evaluate while a stateful solver (lbf_lbfgs_begin / lbf_slbfgs_begin .. *_end) is open, use a second
+ * lbf_mlp of the same shape between two *_iterate calls: the parameters live outside the networks, so the second
+ * one costs only workspace. On the solver's own network this call overwrites the activations, exactly as
+ * lbf_mlp_forward does. */
+typedef struct lbf_eval_result {
+  double loss;
+  long long rows, correct, topk;
+  int k, reserved;
+} lbf_eval_result;
+int lbf_mlp_evaluate(lbf_mlp *net, const float *d_params, const float *d_X, const float *d_Y, const int *d_idx,
+                     long long batch, double inv_scale, int k, long long chunk_rows, lbf_eval_result *h_res,
+                     long long *h_confusion, int *d_pred, float *d_proba);
 int lbf_two_loop(lbf_ctx *ctx, long long n, int k, const float *d_S, const float *d_Y, const double *h_rho,
                  const float *d_g, float *d_dir, int mode);
 

@@ -127,6 +127,15 @@ private:
   size_t n_ = 0;
 };
 
+/// What HipNetwork::evaluate returns (lbf_eval_result): the data loss with inv_scale = 1 / rows, and the counts.
+struct EvalResult {
+  double loss = 0.0;
+  long long rows = 0, correct = 0, topk = 0;
+  int k = 1;
+  double accuracy() const { return rows > 0 ? double(correct) / double(rows) : 0.0; } ///< in [0, 1]
+  double topk_accuracy() const { return rows > 0 ? double(topk) / double(rows) : 0.0; }
+};
+
 /// Dense MLP on the device (CudaNetwork, src/cuda/network.cuh:21-158).
 class HipNetwork {
 public:
@@ -181,6 +190,26 @@ public:
                                 &loss),
               "lbf_mlp_loss_grad");
     return HipScalar(loss);
+  }
+  /// Device-side evaluation (lbf_mlp_evaluate; replaces the host scan of unified_launcher.hpp:154-199): loss,
+  /// correct and top-k counts of `batch` rows; d_y null: predictions only. confusion (nullable): resized to
+  /// Out x Out, [target * Out + predicted]. d_pred (nullable): batch ints on the device. The argmax and top-k
+  /// rules are stated in lbfgs_amd.h. With a communicator `batch` is this rank's share and the result the total.
+  EvalResult evaluate(const HipScalar *d_x, const HipScalar *d_y, long long batch, int k = 1,
+                      std::vector<long long> *confusion = nullptr, int *d_pred = nullptr) {
+    lbf_eval_result r{};
+    const size_t out = size_t(output_size());
+    if (confusion) confusion->assign(out * out, 0);
+    hip_check(lbf_mlp_evaluate(net_, params_.data(), d_x, d_y, nullptr, batch, 1.0, k, 0, &r,
+                               confusion ? confusion->data() : nullptr, d_pred, nullptr),
+              "lbf_mlp_evaluate");
+    EvalResult e;
+    e.rows = r.rows;
+    e.correct = r.correct;
+    e.topk = r.topk;
+    e.k = r.k;
+    e.loss = r.rows > 0 ? r.loss * (1.0 / double(r.rows)) : 0.0; // linear in inv_scale: 1 / total rows
+    return e;
   }
   lbf_mlp *raw() const { return net_; }
   HipHandle &handle() { return h_; }
@@ -589,6 +618,15 @@ public:
     last_train_ = evaluate(train_y_, d_train_x_, n_train_, "Training Results");
   }
   void test() { last_test_ = evaluate(test_y_, d_test_x_, n_test_, "Test Results"); }
+  /// Device-side metrics of the training or the test split (HipNetwork::evaluate) against the fp32 targets that
+  /// setData() uploaded once; prints nothing. evaluate() / train() / test() keep the reference's host scan.
+  hip_mlp::EvalResult metrics(bool test_split, int k = 1, std::vector<long long> *confusion = nullptr) {
+    auto &net = net_wrapper_.getInternal();
+    const long n = test_split ? n_test_ : n_train_;
+    if (n <= 0) return hip_mlp::EvalResult{};
+    return net.evaluate((test_split ? d_test_x_ : d_train_x_).data(), (test_split ? d_test_y_ : d_train_y_).data(), n,
+                        k, confusion);
+  }
   NetworkWrapper<HipBackend> &getWrapper() { return net_wrapper_; }
   std::pair<double, double> lastTrain() const { return last_train_; }
   std::pair<double, double> lastTest() const { return last_test_; }

@@ -61,6 +61,11 @@ class SolveInfo(C.Structure):
                 ("n_grad_after_loss", C.c_longlong)]
 
 
+class EvalResultC(C.Structure):  # lbf_eval_result
+    _fields_ = [("loss", C.c_double), ("rows", C.c_longlong), ("correct", C.c_longlong), ("topk", C.c_longlong),
+                ("k", C.c_int), ("reserved", C.c_int)]
+
+
 _lib = None
 _vp, _ip, _dp, _fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float)
 
@@ -145,6 +150,8 @@ def lib():
         "lbf_mlp_get_loss": (C.c_int, [_vp, _ip]),
         "lbf_mlp_set_l2": (C.c_int, [_vp, C.c_double]),
         "lbf_mlp_get_l2": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+        "lbf_mlp_evaluate": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_int, C.c_longlong,
+                                       C.POINTER(EvalResultC), _vp, _vp, _vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -163,7 +170,7 @@ EXPORTS = ("lbf_last_error lbf_version lbf_abi_version lbf_ctx_create lbf_ctx_de
            "lbf_lbfgs_begin lbf_lbfgs_iterate lbf_lbfgs_end lbf_lbfgs_solve_fn lbf_device_alloc lbf_device_free lbf_memcpy lbf_slbfgs_solve lbf_slbfgs_begin lbf_slbfgs_iterate lbf_slbfgs_end lbf_slbfgs_pair0 lbf_slbfgs_pair_io lbf_prof_enable lbf_prof_select lbf_prof_sample lbf_prof_read lbf_prof_read_work lbf_synth_mnist "
            "lbf_sample_indices lbf_synth_regression lbf_gd_default_params lbf_sgd_default_params lbf_gd_solve "
            "lbf_sgd_solve lbf_idx_read_images lbf_idx_read_labels lbf_mlp_hvp lbf_mlp_fd_hvp lbf_mlp_loss "
-           "lbf_mlp_set_loss lbf_mlp_get_loss lbf_mlp_set_l2 lbf_mlp_get_l2").split()
+           "lbf_mlp_set_loss lbf_mlp_get_loss lbf_mlp_set_l2 lbf_mlp_get_l2 lbf_mlp_evaluate").split()
 
 
 def check_l2(l2) -> float:

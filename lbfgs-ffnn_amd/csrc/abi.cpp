@@ -311,6 +311,23 @@ int lbf_mlp_get_l2(const lbf_mlp *net, double *l2) {
   });
 }
 
+int lbf_mlp_evaluate(lbf_mlp *net, const float *d_params, const float *d_X, const float *d_Y, const int *d_idx,
+                     long long batch, double inv_scale, int k, long long chunk_rows, lbf_eval_result *h_res,
+                     long long *h_confusion, int *d_pred, float *d_proba) {
+  return guard([&] {
+    LBF_REQUIRE(net && d_params && h_res && batch >= 0 && (batch == 0 || d_X) && chunk_rows >= 0, "bad argument");
+    net->ctx->c.set_device();
+    const Mlp::EvalTotals t =
+        net->net->evaluate(d_params, d_X, d_Y, d_idx, batch, k, chunk_rows, h_confusion, d_pred, d_proba);
+    h_res->loss = 0.5 * t.sse * inv_scale;
+    h_res->rows = t.rows;
+    h_res->correct = t.correct;
+    h_res->topk = t.topk;
+    h_res->k = k;
+    h_res->reserved = 0;
+  });
+}
+
 int lbf_mlp_fd_hvp(lbf_mlp *net, const float *d_params, const float *d_v, const float *d_X, const float *d_Y,
                    const int *d_idx, long long batch, double inv_scale, double l2, double eps, float *d_y) {
   return guard([&] {

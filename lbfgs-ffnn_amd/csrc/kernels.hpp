@@ -140,6 +140,33 @@ void loss_diff(hipStream_t s, const float *Aout, long long lda, const float *Y, 
 void loss_xent(hipStream_t s, const float *Z, long long ldz_in, const float *Y, long long ldy, const int *idx,
                long long B, int Out, double inv_scale, float *dZ, long long ldz, double *partials);
 
+// Evaluation metrics of stored outputs (metrics.hip; the argmax and top-k rules are stated there). Z [B][Out]
+// dense; Y (nullable: predictions only) gathered through idx as above. Per workgroup w < metrics_nwg(B, Out):
+// partials[w] = this workgroup's sum of (z - y)^2 (LOSS_MSE) or 2 y (lse - z) (LOSS_XENT), so 0.5 inv_scale times
+// their sum is the data loss, as for every head. cpart[3 w + 0..2] = the workgroup's rows, rows with pred == tgt,
+// rows whose target has rank < k; conf [Out][Out] += 1 at [tgt][pred] (integer atomics) when conf_mode != 0;
+// pred [B] (nullable) the predicted class per row; proba [B][Out] (nullable, LOSS_XENT only) softmax(Z).
+struct MetricsArgs {
+  const float *Z = nullptr, *Y = nullptr;
+  const int *idx = nullptr;
+  long long B = 0;
+  int Out = 0, loss = LOSS_MSE, k = 1;
+  int conf_mode = 0; // 0: none, 1: privatised in LDS (Out <= 64), 2: global atomics per row
+  double *partials = nullptr;
+  unsigned *cpart = nullptr;
+  unsigned long long *conf = nullptr;
+  int *pred = nullptr;
+  float *proba = nullptr;
+};
+int metrics_nwg(long long B, int Out);
+int metrics_conf_mode(int Out, bool want);
+void metrics(hipStream_t s, const MetricsArgs &a);
+// One workgroup: sum[0] = the npart partials summed in a fixed order, words[0..1] = that sum as fp32 (hi, lo),
+// words[2 + 3 c ..] = count c as three 16-bit limbs held as floats (eval_limbs.hpp): c < 3 the column sums of
+// cpart [npart][3], then the nconf cells of conf.
+void metrics_finish(hipStream_t s, const double *partials, const unsigned *cpart, int npart,
+                    const unsigned long long *conf, int nconf, double *sum, float *words);
+
 // Fused output layer (head.hip): forward + MSE + dZ + delta_prev + per-tile [dW ; db] slabs.
 bool head_supported(int H, int Out);
 int head_tile(int H);

@@ -1,5 +1,6 @@
 // Context, MLP evaluation plan and device history (see runtime.hpp).
 #include "runtime.hpp"
+#include "eval_limbs.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -281,7 +282,7 @@ void Mlp::ensure(long long B) {
     }
     cap_ = B;
   }
-  plan(B);
+  plan(plan_pin_ > 0 ? plan_pin_ : B);
   const int nl = int(layers_.size());
   const Layer &Lo = layers_[nl - 1];
   size_t nloss = size_t(loss_partials_wg(std::max(1LL, B), Lo.out));
@@ -387,6 +388,81 @@ const float *Mlp::forward(const float *P, const float *X, const int *idx, long l
     in = A_[l].get();
   }
   return in;
+}
+
+Mlp::EvalTotals Mlp::evaluate(const float *P, const float *X, const float *Y, const int *idx, long long B, int k,
+                              long long chunk_rows, long long *h_conf, int *d_pred, float *d_proba) {
+  const Layer &Lo = layers_.back();
+  const int Out = Lo.out, In = layers_.front().in;
+  LBF_REQUIRE(B >= 0 && chunk_rows >= 0, "evaluate: negative batch or chunk");
+  LBF_REQUIRE(P && (B == 0 || X), "evaluate: null argument");
+  LBF_REQUIRE(k >= 1 && k <= Out, "evaluate: k outside 1..Out");
+  LBF_REQUIRE(!h_conf || Y || B == 0, "evaluate: a confusion matrix needs targets");
+  LBF_REQUIRE(!d_proba || loss_ == LOSS_XENT, "evaluate: probabilities need the softmax cross-entropy loss");
+  LBF_REQUIRE(!ctx_->dp() || ctx_->nranks <= kEvalMaxRanks, "evaluate: at most 256 ranks");
+  LBF_REQUIRE(B <= kEvalMaxCount, "evaluate: batch too large");
+  hipStream_t s = ctx_->stream;
+  const long long chunk = std::max(1LL, std::min(chunk_rows > 0 ? chunk_rows : 65536LL, std::max(1LL, B)));
+  const long long nchunks = cdiv(B, chunk);
+  const int ncounts = 3 + (h_conf ? Out * Out : 0);
+  const size_t nwords = 2 + size_t(kEvalLimbs) * size_t(ncounts);
+  const size_t part_cap = size_t(std::max(1LL, nchunks)) * size_t(metrics_nwg(chunk, Out));
+  const int nconf = h_conf ? Out * Out : 0;
+  ev_part_.ensure(part_cap);
+  ev_cpart_.ensure(3 * part_cap);
+  ev_cnt_.ensure(size_t(std::max(1, nconf)));
+  ev_words_.ensure(nwords);
+  ev_sum_.ensure(1);
+  ev_hwords_.ensure(nwords);
+  ev_hsum_.ensure(1);
+  if (nconf) LBF_HIP(hipMemsetAsync(ev_cnt_.get(), 0, size_t(nconf) * sizeof(unsigned long long), s));
+  int npart = 0;
+  {
+    // every chunk under the whole batch's forward plan: the outputs do not depend on the chunking
+    struct Pin {
+      long long &p;
+      ~Pin() { p = -1; }
+    } pin{plan_pin_};
+    plan_pin_ = B;
+    for (long long r0 = 0; r0 < B; r0 += chunk) {
+      const long long b = std::min(chunk, B - r0);
+      const float *Z = forward(P, idx ? X : X + r0 * In, idx ? idx + r0 : nullptr, b);
+      MetricsArgs a;
+      a.Z = Z;
+      a.Y = Y ? (idx ? Y : Y + r0 * Out) : nullptr;
+      a.idx = idx ? idx + r0 : nullptr;
+      a.B = b;
+      a.Out = Out;
+      a.loss = loss_;
+      a.k = k;
+      a.conf_mode = metrics_conf_mode(Out, h_conf != nullptr);
+      a.partials = ev_part_.get() + npart;
+      a.cpart = ev_cpart_.get() + 3 * size_t(npart);
+      a.conf = h_conf ? ev_cnt_.get() : nullptr;
+      a.pred = d_pred ? d_pred + r0 : nullptr;
+      a.proba = d_proba ? d_proba + r0 * Out : nullptr;
+      {
+        ProfScope ps(ctx_, PK_METRICS, 0, double(b));
+        metrics(s, a);
+      }
+      npart += metrics_nwg(b, Out);
+    }
+  }
+  metrics_finish(s, ev_part_.get(), ev_cpart_.get(), npart, ev_cnt_.get(), nconf, ev_sum_.get(), ev_words_.get());
+  if (ctx_->dp()) ctx_->allreduce(ev_words_.get(), nwords);
+  LBF_HIP(hipMemcpyAsync(ev_hwords_.get(), ev_words_.get(), nwords * sizeof(float), hipMemcpyDeviceToHost, s));
+  LBF_HIP(hipMemcpyAsync(ev_hsum_.get(), ev_sum_.get(), sizeof(double), hipMemcpyDeviceToHost, s));
+  LBF_HIP(hipStreamSynchronize(s));
+  const float *w = ev_hwords_.get();
+  EvalTotals r;
+  // a single rank keeps the fp64 sum; across ranks the loss is what the (hi, lo) words carried
+  r.sse = ctx_->dp() ? double(w[0]) + double(w[1]) : ev_hsum_[0];
+  r.rows = eval_limbs_merge(w + 2);
+  r.correct = eval_limbs_merge(w + 2 + kEvalLimbs);
+  r.topk = eval_limbs_merge(w + 2 + 2 * kEvalLimbs);
+  if (h_conf)
+    for (int c = 0; c < Out * Out; ++c) h_conf[c] = eval_limbs_merge(w + 2 + kEvalLimbs * (3 + c));
+  return r;
 }
 
 void Mlp::set_l2(double l2) {

@@ -13,7 +13,7 @@ namespace lbf {
 
 // Per-kernel-class timing with HIP events on the launch stream (enabled by the benchmark only).
 enum ProfKind : int { PK_FWD = 0, PK_DW = 1, PK_DX = 2, PK_LOSS = 3, PK_SLAB = 4, PK_FINAL = 5, PK_GRAM = 6,
-                      PK_COEF = 7, PK_COMBINE = 8, PK_AXPY = 9, PK_ALLREDUCE = 10 };
+                      PK_COEF = 7, PK_COMBINE = 8, PK_AXPY = 9, PK_ALLREDUCE = 10, PK_METRICS = 11 };
 struct ProfRec { int id; size_t a, b; double work; };
 struct Profiler {
   bool on = false;
@@ -179,6 +179,24 @@ public:
   // R-operator (hvp.hip); with a communicator the shards' products are all-reduced. Hv: nparams().
   void hvp(const float *P, const float *V, const float *X, const float *Y, const int *idx, long long B,
            double inv_scale, double lambda, float *Hv);
+  // Device-side evaluation (metrics.hip; replaces the host scan of unified_launcher.hpp:154-199): forward() and
+  // the metrics kernel per chunk of chunk_rows rows (0: 65536, or the batch if smaller), so the activation
+  // workspace is bounded by the chunk. Every chunk runs the forward plan of the whole batch, so the outputs, and
+  // with them every count, do not depend on the chunking. The chunks' loss partials fill one table in row order,
+  // summed once at the end; counts accumulate on the device; one read-back and one synchronisation per call.
+  // With a communicator each rank passes its B local rows (B == 0: an empty share) and one float all-reduce
+  // carries the loss as (hi, lo) words and every count as three 16-bit limbs (eval_limbs.hpp: exact up to 256
+  // ranks and counts below 2^48); d_pred / d_proba stay local. Y null: predictions only (sse = correct = topk = 0).
+  // h_conf (nullable, needs Y): Out x Out counts [tgt][pred]. All buffers are this Mlp's own: nothing a solver on
+  // another Mlp of the context reads is touched (not the context's status block, its gradient scratch or any
+  // history). Intended use during a stateful solve: a second Mlp of the same shape (parameters are external to
+  // the net, so that costs only workspace); on the solver's own Mlp it overwrites the activations like forward().
+  struct EvalTotals {
+    double sse = 0.0; // sum of the loss partials: data loss = 0.5 * inv_scale * sse
+    long long rows = 0, correct = 0, topk = 0;
+  };
+  EvalTotals evaluate(const float *P, const float *X, const float *Y, const int *idx, long long B, int k,
+                      long long chunk_rows, long long *h_conf, int *d_pred, float *d_proba);
   long long evals() const { return evals_; }
   long long rows() const { return rows_; } // batch rows evaluated (sum of B over loss_grad calls)
   void discard_evals(long long k, long long B) { // speculative evaluations (B rows each) that were aborted
@@ -234,6 +252,15 @@ private:
   std::vector<DevBuf<float>> RZ_, RA_, RD_, DL_;
   DevBuf<float> T1_, T2_, seg_;
   long long rcap_ = -1;
+  // evaluate(): per-workgroup loss partials and counts [rows, correct, topk] of every chunk, the confusion cells,
+  // the partials' sum, the all-reduce words
+  DevBuf<double> ev_part_, ev_sum_;
+  DevBuf<unsigned> ev_cpart_;
+  DevBuf<unsigned long long> ev_cnt_;
+  DevBuf<float> ev_words_;
+  PinnedBuf<float> ev_hwords_;
+  PinnedBuf<double> ev_hsum_;
+  long long plan_pin_ = -1; // > 0: ensure() plans for this many rows whatever the batch (evaluate's chunks)
   long long evals_ = 0, rows_ = 0;
   void plan(long long B);
 };

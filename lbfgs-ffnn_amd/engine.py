@@ -8,13 +8,15 @@ of src/minimizer/s_lbfgs.hpp:165-290 -> :func:`slbfgs_solve`.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
 from ._lib import (ACTS, INIT_CPU, INIT_CUDA, LOSSES, check_l2, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED, SLBFGS_DP_SLICED,
-                   GdParams, LbfError, LbfgsParams, Record, SgdParams, SlbfgsParams, SolveInfo, check, lib, ptr)
+                   EvalResultC, GdParams, LbfError, LbfgsParams, Record, SgdParams, SlbfgsParams, SolveInfo, check, lib,
+                   ptr)
 
 
 class Context:
@@ -85,7 +87,7 @@ class Context:
         return out
 
     PROF_KINDS = ["gemm_fwd", "gemm_dw", "gemm_dx", "loss", "splitk_reduce", "finalize", "gram_sweep",
-                  "hist_coef", "combine_sweep", "ls_axpy", "allreduce"]
+                  "hist_coef", "combine_sweep", "ls_axpy", "allreduce", "metrics"]
 
     def prof_enable(self, on: bool = True):
         check(lib().lbf_prof_enable(self.h, int(on)), "lbf_prof_enable")
@@ -140,6 +142,20 @@ class Context:
                 self.h = None
         except Exception:
             pass
+
+
+@dataclass
+class EvalResult:
+    """What Mlp.evaluate returns (lbf_eval_result + the optional outputs). accuracy = correct / rows in [0, 1]."""
+    loss: float
+    rows: int
+    correct: int
+    topk: int
+    k: int
+    accuracy: float
+    confusion: Optional[np.ndarray] = None   # [target][predicted] int64
+    pred: Optional[torch.Tensor] = None      # int32 [rows of this rank], batch order
+    proba: Optional[torch.Tensor] = None     # float32 [rows of this rank][Out]
 
 
 class Mlp:
@@ -259,6 +275,43 @@ class Mlp:
         check(lib().lbf_mlp_loss(self.h, ptr(params, numel=self.nparams), ptr(X), ptr(Y), ptr(idx, torch.int32), B,
                                  inv_scale, C.byref(out)), "lbf_mlp_loss")
         return out.value
+
+    def evaluate(self, params: torch.Tensor, X: torch.Tensor, Y: Optional[torch.Tensor] = None,
+                 idx: Optional[torch.Tensor] = None, inv_scale: Optional[float] = None, k: int = 1,
+                 confusion: bool = False, pred: bool = False, proba: bool = False, chunk: int = 0) -> "EvalResult":
+        """Device-side evaluation (lbf_mlp_evaluate): data loss, accuracy, top-k, and on request the confusion
+        matrix [target][predicted], the predicted class per row (batch order) and the softmax probabilities
+        (cross-entropy networks). Y None: predictions only. With a communicator X / Y are this rank's rows (an
+        empty share is legal) and the counts and the loss are the totals over all ranks; inv_scale then defaults
+        to 1 / total rows. chunk: rows per forward pass (0: 65536). The argmax and top-k rules are those of
+        include/lbfgs_amd.h. To evaluate while an LbfgsRun / SlbfgsRun is open, use a second Mlp of the same shape."""
+        B = int(idx.numel()) if idx is not None else int(X.shape[0])
+        Out = self.dims[-1]
+        if not 1 <= int(k) <= Out:
+            raise LbfError(f"k must be in 1..{Out}, got {k}")
+        if confusion and Y is None:
+            raise LbfError("a confusion matrix needs targets")
+        if proba and self.loss_name != "softmax_xent":
+            raise LbfError("probabilities need the softmax_xent loss")
+        if Y is not None and idx is None:
+            self._check_data(X, Y)
+        else:
+            self._check_data(X, None)
+        dev = X.device
+        res = EvalResultC()
+        conf = np.zeros((Out, Out), np.int64) if confusion else None
+        d_pred = torch.empty(B, dtype=torch.int32, device=dev) if pred else None
+        d_proba = torch.empty((B, Out), dtype=torch.float32, device=dev) if proba else None
+        # the loss is linear in inv_scale: evaluate with 1 and scale by the default once the total rows are known
+        check(lib().lbf_mlp_evaluate(self.h, ptr(params, numel=self.nparams), ptr(X), ptr(Y), ptr(idx, torch.int32), B,
+                                     1.0 if inv_scale is None else float(inv_scale), int(k), int(chunk), C.byref(res),
+                                     conf.ctypes.data_as(C.c_void_p) if confusion else None,
+                                     ptr(d_pred, torch.int32), ptr(d_proba)), "lbf_mlp_evaluate")
+        rows = int(res.rows)
+        loss = float(res.loss) if inv_scale is not None else float(res.loss) * (1.0 / max(rows, 1))
+        return EvalResult(loss=loss, rows=rows, correct=int(res.correct), topk=int(res.topk), k=int(k),
+                          accuracy=(int(res.correct) / rows if rows and Y is not None else 0.0), confusion=conf,
+                          pred=d_pred, proba=d_proba)
 
     def hvp(self, params: torch.Tensor, v: torch.Tensor, X: torch.Tensor, Y: torch.Tensor,
             idx: Optional[torch.Tensor] = None, inv_scale: Optional[float] = None, l2: float = 0.0,

@@ -50,6 +50,12 @@ class UnifiedConfig:
                                  # like UnifiedLauncher.setLoss, and it then stays the network's loss)
     l2: float = 0.0              # weight decay of UnifiedLBFGS / UnifiedGD / UnifiedSGD (HIP extension; train()
                                  # applies a non-zero value like UnifiedLauncher.setL2, and it then stays)
+    # Validation-monitored training (HIP extension; UnifiedLBFGS and UnifiedSLBFGS). eval_every > 0: the test split
+    # is evaluated on the device at iteration 0, every eval_every iterations (epochs for S-LBFGS) and at the end.
+    eval_every: int = 0          # 0: off (the unmonitored code path)
+    patience: int = 0            # stop after this many evaluations in a row without a strict improvement; 0: never
+    monitor: str = "loss"        # "loss" (lower is better) or "accuracy" (higher is better)
+    restore_best: bool = True    # finish with the parameters of the best evaluation
 
 
 @dataclass
@@ -66,12 +72,14 @@ class IterationRecorder:
 
     def __init__(self):
         self.loss, self.grad_norm, self.time_ms = [], [], []
+        self.validation = []   # (iteration, val_loss, val_accuracy) of a validation-monitored run
 
     def init(self, capacity: int):
         self.reset()
 
     def reset(self):
         self.loss, self.grad_norm, self.time_ms = [], [], []
+        self.validation = []
 
     def record(self, idx: int, loss: float, grad_norm: float, time_ms: float = 0.0):
         while len(self.loss) <= idx:
@@ -147,10 +155,131 @@ class UnifiedOptimizer:
         raise NotImplementedError
 
 
+class EarlyStopper:
+    """Decides when validation-monitored training stops: after `patience` evaluations in a row that bring no
+    strict improvement of the monitored value ("loss": lower is better, "accuracy": higher is better). A tie is
+    not an improvement, neither is a NaN; the first evaluation always counts as one. patience == 0 never stops.
+    Pure Python: update(iteration, loss, accuracy) returns True when training should stop; best_iteration,
+    best_loss and best_accuracy name the best evaluation so far."""
+
+    def __init__(self, patience: int = 0, monitor: str = "loss"):
+        if monitor not in ("loss", "accuracy"):
+            raise LbfError(f"monitor must be 'loss' or 'accuracy', got {monitor!r}")
+        if int(patience) < 0:
+            raise LbfError(f"patience must be >= 0, got {patience!r}")
+        self.patience, self.monitor = int(patience), monitor
+        self.best_iteration: Optional[int] = None
+        self.best_loss = self.best_accuracy = None
+        self.stale = 0   # evaluations since the best one
+
+    def improved(self, loss: float, accuracy: float) -> bool:
+        if self.best_iteration is None:
+            return True
+        return accuracy > self.best_accuracy if self.monitor == "accuracy" else loss < self.best_loss
+
+    def update(self, iteration: int, loss: float, accuracy: float) -> bool:
+        if self.improved(loss, accuracy):
+            self.best_iteration, self.best_loss, self.best_accuracy = int(iteration), loss, accuracy
+            self.stale = 0
+        else:
+            self.stale += 1
+        return self.patience > 0 and self.stale >= self.patience
+
+
+def validation_filename(config: UnifiedConfig) -> str:
+    return (config.name or "run") + "_validation.csv"
+
+
+def write_validation_csv(filename: str, validation) -> None:
+    """`Iteration,ValLoss,ValAccuracy`, one line per evaluation of the monitored run."""
+    with open(filename, "w") as f:
+        f.write("Iteration,ValLoss,ValAccuracy\n")
+        for it, loss, acc in validation:
+            f.write(f"{it},{loss:.17g},{acc:.17g}\n")
+
+
+def _check_monitored(config: UnifiedConfig, data: "_DeviceData") -> None:
+    if config.monitor not in ("loss", "accuracy"):
+        raise LbfError(f"monitor must be 'loss' or 'accuracy', got {config.monitor!r}")
+    if data is None or data.test_xs is None or data.n_test == 0:
+        raise LbfError("eval_every > 0 needs a test split (UnifiedDataset.test_x / test_y)")
+
+
+def _assert_ranks_agree(entry) -> None:
+    """Every rank must hold bitwise the same validation entry, or the ranks would stop at different iterations."""
+    if not (torch.distributed.is_available() and torch.distributed.is_initialized()):
+        return
+    world = torch.distributed.get_world_size()
+    if world == 1:
+        return
+    mine = (int(entry[0]), float(entry[1]).hex(), float(entry[2]).hex())
+    seen = [None] * world
+    torch.distributed.all_gather_object(seen, mine)
+    if any(s != mine for s in seen):
+        raise LbfError(f"validation metrics differ between ranks: {seen}")
+
+
+def _monitored_run(optimizer: "UnifiedOptimizer", net: _DeviceNet, data: "_DeviceData", config: UnifiedConfig, run):
+    """Drive a resumable solver (`run`: LbfgsRun / SlbfgsRun on net.mlp) in chunks of config.eval_every iterations,
+    evaluating the test split between the chunks on a second Mlp of the same shape (the solver's own network and
+    workspace are never touched). Sets optimizer.validation = [(iteration, val_loss, val_accuracy)],
+    optimizer.best_iteration and optimizer.stopped_early; with restore_best the best parameters are copied back."""
+    ev_net = engine.Mlp(net.ctx, net.mlp.dims, net.mlp.acts, loss=net.loss)
+    stopper = EarlyStopper(config.patience, config.monitor)
+    best = torch.empty_like(net.params) if config.restore_best else None
+    validation = []
+
+    def observe(it: int) -> bool:
+        r = ev_net.evaluate(net.params, data.test_xs, data.test_ys)
+        entry = (it, r.loss, r.accuracy)
+        _assert_ranks_agree(entry)
+        validation.append(entry)
+        stop = stopper.update(*entry)
+        if best is not None and stopper.best_iteration == it:
+            best.copy_(net.params)
+        return stop
+
+    it = 0
+    try:
+        stop = observe(0)
+        while not stop and it < config.max_iters:
+            n = min(int(config.eval_every), config.max_iters - it)
+            now = int(run.iterate(n).iterations)
+            if now == it:   # converged on entry: the last evaluation is the final one
+                break
+            ended = now - it < n
+            it = now
+            stop = observe(it) or ended
+    finally:
+        run.close()
+    if best is not None and stopper.best_iteration != it:
+        net.params.copy_(best)
+    torch.cuda.synchronize(net.ctx.device)
+    optimizer.validation = validation
+    optimizer.best_iteration = stopper.best_iteration
+    optimizer.stopped_early = bool(stopper.patience > 0 and stopper.stale >= stopper.patience)
+    hist = run.hist.as_dict()
+    rec = IterationRecorder()
+    for i in range(len(hist["loss"])):
+        rec.record(i, float(hist["loss"][i]), float(hist["grad_norm"][i]), float(hist["time_ms"][i]))
+    rec.validation = list(validation)
+    optimizer.info = run.info
+    optimizer.history = hist
+    return rec
+
+
 class UnifiedLBFGS(UnifiedOptimizer):
-    """UnifiedLBFGS<HipBackend> (unified_optimization.hpp:191-214 / 560-592)."""
+    """UnifiedLBFGS<HipBackend> (unified_optimization.hpp:191-214 / 560-592). config.eval_every > 0: the same solve
+    through LbfgsRun in chunks, with validation, early stopping and restore_best (_monitored_run)."""
 
     def optimize(self, net, data, config):
+        if config.eval_every > 0:
+            _check_monitored(config, data)
+            run = engine.LbfgsRun(net.mlp, net.params, data.x, data.y, n_global=data.n_global,
+                                  line_search=config.line_search, record_cap=max(config.max_iters, 1),
+                                  m=config.m_param if config.m_param > 0 else 10, max_iters=config.max_iters,
+                                  tol=config.tolerance)
+            return _monitored_run(self, net, data, config, run)
         hist, info = engine.lbfgs_solve(net.mlp, net.params, data.x, data.y, n_global=data.n_global,
                                         line_search=config.line_search, m=config.m_param if config.m_param > 0 else 10,
                                         max_iters=config.max_iters, tol=config.tolerance)
@@ -169,6 +298,12 @@ class UnifiedSLBFGS(UnifiedOptimizer):
 
     def optimize(self, net, data, config):
         b_H = config.b_H_param if config.b_H_param > 0 else config.batch_size // 2   # :325
+        if config.eval_every > 0:   # the same solve through SlbfgsRun, an epoch per iteration (_monitored_run)
+            _check_monitored(config, data)
+            run = engine.SlbfgsRun(net.mlp, net.params, data.x_full, data.y_full, record_cap=max(config.max_iters, 1),
+                                   tol=config.tolerance, M=config.m_param, L=config.L_param, b=config.batch_size,
+                                   b_H=b_H, step=config.learning_rate, lam=1e-4, seed=123)
+            return _monitored_run(self, net, data, config, run)
         hist, info = engine.slbfgs_solve(net.mlp, net.params, data.x_full, data.y_full, max_epochs=config.max_iters,
                                          tol=config.tolerance, M=config.m_param, L=config.L_param,
                                          b=config.batch_size, b_H=b_H, step=config.learning_rate, lam=1e-4,
@@ -186,6 +321,8 @@ class UnifiedGD(UnifiedOptimizer):
     momentum, max_iters, tolerance)."""
 
     def optimize(self, net, data, config):
+        if config.eval_every > 0:
+            raise LbfError("UnifiedGD has no resumable form: eval_every > 0 needs UnifiedLBFGS or UnifiedSLBFGS")
         hist, info = engine.gd_solve(net.mlp, net.params, data.x, data.y, n_global=data.n_global,
                                      lr=config.learning_rate, momentum=config.momentum, max_iters=config.max_iters,
                                      tol=config.tolerance)
@@ -203,6 +340,8 @@ class UnifiedSGD(UnifiedOptimizer):
     not passed, so CudaSGD's default 1e-6 applies). Single rank."""
 
     def optimize(self, net, data, config):
+        if config.eval_every > 0:
+            raise LbfError("UnifiedSGD has no resumable form: eval_every > 0 needs UnifiedLBFGS or UnifiedSLBFGS")
         hist, info = engine.sgd_solve(net.mlp, net.params, data.x_full, data.y_full, lr=config.learning_rate,
                                       momentum=config.momentum, batch=config.batch_size, max_epochs=config.max_iters,
                                       decay_rate=config.lr_decay, decay_step=config.lr_decay_rate)
@@ -232,6 +371,14 @@ class _DeviceData:
             if dataset.test_x.size else None
         self.test_y = np.asarray(dataset.test_y, np.float64)
         self.train_y_host = np.asarray(dataset.train_y, np.float64)
+        # this rank's contiguous shard of the test split and its targets, device-resident (metrics(), validation)
+        self.n_test = int(dataset.test_x.shape[0]) if dataset.test_x.size else 0
+        self.test_xs = self.test_ys = None
+        if self.n_test:
+            ey = np.ascontiguousarray(dataset.test_y, np.float32)
+            tlo, thi = self.n_test * rank // world, self.n_test * (rank + 1) // world
+            self.test_xs = self.test_x if world == 1 else self.test_x[tlo:thi].contiguous()
+            self.test_ys = torch.from_numpy(ey[tlo:thi]).to(device)
         torch.cuda.synchronize()
 
 
@@ -287,6 +434,8 @@ class UnifiedLauncher:
         recorder = optimizer.optimize(self.net_wrapper_, self.data_, config)
         if config.write_csv and self.rank == 0:
             write_history_csv(log_filename(config), recorder, config.log_interval)
+        if config.eval_every > 0 and config.write_csv and self.rank == 0:
+            write_validation_csv(validation_filename(config), recorder.validation)
         self.last_recorder = recorder
         return self.evaluate(self.data_.x_full if self.world == 1 else self.data_.x_full,
                              self.data_.train_y_host, "Training Results")
@@ -311,6 +460,24 @@ class UnifiedLauncher:
         if self.rank == 0:
             print(f"{label}: MSE={mse:g}, Accuracy={acc:g}%")
         return dict(mse=mse, accuracy=acc)
+
+    def metrics(self, split: str = "train", k: int = 1, confusion: bool = False):
+        """Device-side evaluation of a split (engine.Mlp.evaluate): loss, accuracy, top-k and optionally the
+        confusion matrix, as an engine.EvalResult. Under data parallelism each rank evaluates its contiguous shard
+        and every rank gets the same totals. Prints nothing. It runs on a network of its own, so it may be called
+        while a solver is open on the launcher's network."""
+        if split not in ("train", "test"):
+            raise LbfError(f"split must be 'train' or 'test', got {split!r}")
+        d = self.data_
+        if d is None or (split == "test" and d.test_xs is None):
+            raise LbfError(f"no {split} split: call setData() with one first")
+        nw = self.net_wrapper_
+        if getattr(self, "eval_mlp_", None) is None:
+            self.eval_mlp_ = engine.Mlp(self.ctx, nw.mlp.dims, nw.mlp.acts, loss=nw.loss)
+        elif self.eval_mlp_.loss_name != nw.loss:
+            self.eval_mlp_.loss_name = nw.loss
+        x, y = (d.x, d.y) if split == "train" else (d.test_xs, d.test_ys)
+        return self.eval_mlp_.evaluate(nw.params, x, y, k=k, confusion=confusion)
 
     def getWrapper(self):
         return self.net_wrapper_
