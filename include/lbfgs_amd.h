@@ -5,6 +5,8 @@
  * Conventions:
  *   - return value: LBF_OK (0) or an error code; lbf_last_error() gives the message (thread-local).
  *   - d_* arguments are device pointers (hipMalloc'd or torch tensors' data_ptr), h_* are host pointers.
+ *   - d_* float pointers need 4-byte alignment only; 16-byte-aligned ones take faster routes; lbf_two_loop
+ *     mode 3 is the exception (it returns LBF_ERR_INVALID unless d_S, d_Y, d_g and d_dir are 16-byte aligned).
  *   - calls are asynchronous on the context stream unless they return a host value.
  *   - parameter layout is the reference's flat vector: per layer [W (Out x In, column-major) | b (Out)]
  *     (src/network.hpp:45-71, src/cuda/network.cuh:36-59); data X is In x N column-major and Y is

@@ -694,6 +694,12 @@ __global__ __launch_bounds__(256) void axpy_to_kernel(long long n, const float *
     for (long long j = e; j < n; ++j) y[j] = x[j] + alpha * p[j];
   }
 }
+// x, p or y off a 16-B boundary (a caller's pointer, lbf_axpy): one element per thread, the same fp32 expression
+__global__ __launch_bounds__(256) void axpy_to_elem_kernel(long long n, const float *x, float alpha, const float *p,
+                                                           float *y) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) y[e] = x[e] + alpha * p[e];
+}
 // w.w partials (kernels.hpp WwPart): one word per block of E = ww_block_elems(n) elements.
 long long ww_block_elems(long long n) {
   long long e = 256;
@@ -777,7 +783,11 @@ void axpy_to(hipStream_t s, long long n, const float *x, float alpha, const floa
     LBF_KERNEL_CHECK();
     return;
   }
-  hipLaunchKernelGGL(axpy_to_kernel, dim3(unsigned(cdiv(cdiv(n, 4), 256))), dim3(256), 0, s, n, x, alpha, p, y);
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(y);
+  if ((bits & 15u) == 0)
+    hipLaunchKernelGGL(axpy_to_kernel, dim3(unsigned(cdiv(cdiv(n, 4), 256))), dim3(256), 0, s, n, x, alpha, p, y);
+  else if (n > 0)
+    hipLaunchKernelGGL(axpy_to_elem_kernel, dim3(unsigned(cdiv(n, 256))), dim3(256), 0, s, n, x, alpha, p, y);
   LBF_KERNEL_CHECK();
   if (ww_part) ww_partials(s, n, y, ww_part); // large n: the partials of wider blocks in a launch of their own
 }
@@ -1558,6 +1568,38 @@ __global__ __launch_bounds__(256) void combine_small_kernel(const CombineArgs a)
   }
 }
 
+// The streaming regime with g, dir, x_in, x_out or x_out2 off a 16-B boundary (a caller's pointer, lbf_two_loop):
+// one element per thread, grid-stride, every access 4 bytes; the fp64 sum in combine_chunk_kernel's order (bitwise
+// its result).
+__global__ __launch_bounds__(256) void combine_elem_kernel(const CombineArgs a) {
+  if (a.h.abort && *a.h.abort) return;
+  __shared__ double cs[COEF_MAXK], cy[COEF_MAXK];
+  __shared__ int L[COEF_MAXK];
+  const HistView &h = a.h;
+  const int S_ = h.slots;
+  const int k = h.ist[IST_COUNT];
+  for (int i = threadIdx.x; i < k; i += blockDim.x) {
+    cs[i] = h.coef[i];
+    cy[i] = h.coef[S_ + i];
+    L[i] = h.ist[IST_ORDER + i];
+  }
+  __syncthreads();
+  const double cg = h.coef[2 * S_];
+  const double alpha = a.alpha_from_state ? h.scal[SC_ALPHA0] : a.alpha;
+  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < h.n; q += (long long)gridDim.x * blockDim.x) {
+    double ac = cg * double(a.g[q]);
+    for (int i = 0; i < k; ++i)
+      ac += cs[i] * double(h.S[(long long)L[i] * h.ld + q]) + cy[i] * double(h.Y[(long long)L[i] * h.ld + q]);
+    const float d = float(ac);
+    if (a.dir) a.dir[q] = d;
+    if (a.x_out) {
+      const float o = a.x_in[q] + float(alpha) * d;
+      a.x_out[q] = o;
+      if (a.x_out2) a.x_out2[q] = o;
+    }
+  }
+}
+
 static void combine_stream(hipStream_t s, const CombineArgs &a); // n > 2^21 or m > 32
 
 void hist_combine(hipStream_t s, const CombineArgs &ca) {
@@ -1594,6 +1636,12 @@ static void combine_stream(hipStream_t s, const CombineArgs &a) {
     return (long long)std::max(1, cus) * std::max(1, std::min(p1, p2));
   }();
   const dim3 grid(unsigned(std::min(cdiv(a.h.n, 4096LL), resident)));
+  auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }; // null passes
+  if (!(al16(a.g) && al16(a.dir) && al16(a.x_in) && al16(a.x_out) && al16(a.x_out2))) { // the ring is the engine's own
+    hipLaunchKernelGGL(combine_elem_kernel, dim3(unsigned(std::min(cdiv(a.h.n, 256LL), 16 * resident))), dim3(256), 0, s, a);
+    LBF_KERNEL_CHECK();
+    return;
+  }
   if (hist_nt(a.h))
     hipLaunchKernelGGL((combine_chunk_kernel<2, true>), grid, dim3(256), 0, s, a);
   else
