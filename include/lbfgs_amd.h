@@ -119,6 +119,25 @@ int lbf_mlp_loss_grad(lbf_mlp *net, const float *d_params, float *d_grad, const 
  * Replaces, as an option, the finite-difference HVP of s_lbfgs.hpp:88-101. */
 int lbf_mlp_hvp(lbf_mlp *net, const float *d_params, const float *d_v, const float *d_X, const float *d_Y,
                 const int *d_idx, long long batch, double inv_scale, double l2, float *d_hv);
+/* Generalized Gauss-Newton vector product of the same batch loss (extension; same inv_scale / l2 / d_idx meaning,
+ * argument checks, 4-byte pointer alignment and error codes as lbf_mlp_hvp): d_gv = J^T H_L J d_v + l2 d_v, with
+ * J the Jacobian of the network up to where the convex loss begins and H_L that loss's Hessian. The split is at
+ * the post-activation outputs A_L for LBF_LOSS_MSE (H_L = inv_scale I) and at the logits for
+ * LBF_LOSS_SOFTMAX_XENT (H_L = inv_scale Ysum (diag p - p p^T), p = softmax). With Z_l = A_{l-1} W_l + b_l,
+ * A_l = act_l(Z_l), s = inv_scale and d_v = [V_l ; v_l] in the parameter layout:
+ *   R-forward   T_l     = A_{l-1} V_l + v_l                  (l = 0: X V_0 + v_0, rows gathered by d_idx)
+ *               R{Z_l}  = T_l + R{A_{l-1}} W_l               (l >= 1; the second product has no bias)
+ *               R{A_l}  = act'_l(A_l) .* R{Z_l}              (hidden layers)
+ *   output      M_L     = s act'_L(A_L)^2 .* R{Z_L}                          (LBF_LOSS_MSE)
+ *               M_L     = s Ysum p .* (R{Z_L} - sum_k p_k R{Z_L}_k)          (LBF_LOSS_SOFTMAX_XENT)
+ *   backward    (G v)_l = [A_{l-1} | 1]^T M_l,   M_{l-1} = (M_l W_l^T) .* act'_{l-1}(A_{l-1})
+ * act' is taken through the post-activation value (ReLU: [a > 0]). G is positive semi-definite for both losses
+ * and has no term from an activation's kink or curvature: v.Gv >= l2 v.v. It is the exact product without
+ * (A_L - y) act''_L, [R{A_{l-1}} | 0]^T dZ_l, dZ_l V_l^T and delta act'' R{Z}; the two agree for a single linear
+ * layer and at zero residual. One forward, the R-forward and one backward pass; no finite differences. With a
+ * communicator the shards' products are summed (one all-reduce, before the l2 term); batch == 0 gives l2 d_v. */
+int lbf_mlp_gnvp(lbf_mlp *net, const float *d_params, const float *d_v, const float *d_X, const float *d_Y,
+                 const int *d_idx, long long batch, double inv_scale, double l2, float *d_gv);
 /* Per-minibatch gradients at one point (extension; the reference evaluates them one step at a time:
  * SLBFGS::stochastic_solve's batch_g(w) of every inner step, s_lbfgs.hpp:218-230, at the epoch's fixed anchor
  * w): rows [t cnt, (t+1) cnt) of d_X / d_Y are minibatch t, t < nmb; its gradient of
@@ -225,8 +244,11 @@ typedef struct lbf_slbfgs_params {
   double lambda;      /* L2, 1e-4 in the reference (unified_optimization.hpp:334)    */
   unsigned seed;      /* kDefaultSeed = 123 (src/seed.hpp:4; s_lbfgs.hpp:183)        */
   double fd_eps;      /* finite-difference HVP epsilon, 1e-4 (s_lbfgs.hpp:90)        */
-  int hvp_exact;      /* 0: the reference's central-difference HVP (s_lbfgs.hpp:88-101); 1: the
-                         exact R-operator product (lbf_mlp_hvp), SURVEY §8(f) rank 4          */
+  int hvp_exact;      /* the curvature pair's y: LBF_HVP_FD (0) the reference's central-difference HVP
+                         (s_lbfgs.hpp:88-101); LBF_HVP_EXACT (1) the exact R-operator product
+                         (lbf_mlp_hvp); LBF_HVP_GAUSS_NEWTON (2) the Gauss-Newton
+                         product (lbf_mlp_gnvp): y.s >= lambda s.s > 0 for every pair. Any other
+                         non-zero value is taken as LBF_HVP_EXACT                              */
   /* ABI 2, diagnostics (NULL / 0: off): one row of LBF_PAIR_TRACE_COLS doubles per curvature-pair
    * candidate (s_lbfgs.hpp:245-256): epoch, inner step t, y.s, s.s, y.y, accepted (|y.s| > 1e-10), live
    * pairs after it, 0. Reading each row back synchronises the stream: not for timed runs. */
@@ -242,6 +264,9 @@ typedef struct lbf_slbfgs_params {
 #define LBF_PAIR_TRACE_COLS 8
 #define LBF_SLBFGS_DP_REPLICATED 0
 #define LBF_SLBFGS_DP_SLICED 1
+#define LBF_HVP_FD 0
+#define LBF_HVP_EXACT 1
+#define LBF_HVP_GAUSS_NEWTON 2
 
 /* Gradient descent with momentum == cuda_mlp::CudaGD (src/cuda/gd.cuh:38-106; setters :22-25). */
 typedef struct lbf_gd_params {
@@ -340,7 +365,8 @@ int lbf_slbfgs_pair0(lbf_slbfgs *s, float *d_wt, float *d_u, float *d_s, float *
  * first, which only pushes u, included; with ld = (n + 3) & ~3, event e (counted over epochs, e < cap):
  *   d_rec   (nullable) receives [w_{t+1} | u | g(u + eps s) | g(u - eps s)] at d_rec + 4 e ld (ld floats each;
  *           the two gradients of the batch loss + lambda w, zero at the first event; with hvp_exact the second
- *           is zero and the first is H(u) s);
+ *           is zero and the first is H(u) s + lambda s; in mode LBF_HVP_GAUSS_NEWTON the record holds
+ *           G(u) s + lambda s (lbf_mlp_gnvp on the Hessian batch), then zeros);
  *   d_force (nullable, same layout, e.g. another run's d_rec) replaces u before s = u - u_prev and the two
  *           gradients before y = (g+ - g-) / (2 eps) is stored, so the ring receives the other run's pairs
  *           while the iterates w_t stay this run's own. Two routes forced with one run's record then compare

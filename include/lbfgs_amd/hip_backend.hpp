@@ -416,6 +416,9 @@ struct UnifiedConfig {
   bool reset_params = true;
   unsigned int seed = 123u;
   double l2 = 0.0; ///< HIP extension: train() applies a non-zero value like UnifiedLauncher::setL2
+  /// HIP extension: UnifiedSLBFGS_HIP's curvature pairs, LBF_HVP_FD (the reference's finite difference),
+  /// LBF_HVP_EXACT or LBF_HVP_GAUSS_NEWTON (lbf_slbfgs_params.hvp_exact)
+  int curvature = LBF_HVP_FD;
 };
 /// src/unified_optimization.hpp:54-59 (HostMatrix instead of Eigen::MatrixXd)
 struct UnifiedDataset {
@@ -516,6 +519,9 @@ public:
     prm.b = c.batch_size;
     prm.b_H = c.b_H_param > 0 ? c.b_H_param : c.batch_size / 2;
     prm.step = c.learning_rate;
+#ifndef LBF_USE_REFERENCE_UNIFIED_TYPES // the reference's own UnifiedConfig has no such member
+    prm.hvp_exact = c.curvature;
+#endif
     recorder.init(c.max_iters);
     lbf_record rec = recorder.view();
     lbf_solve_info info{};

@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 ABI_VERSION = 3  # include/lbfgs_amd.h LBF_ABI_VERSION (also in the library's file name)
 LIB_PATH = os.environ.get("LBF_LIB_PATH") or os.path.join(_HERE, "build", f"liblbfgs_amd_abi{ABI_VERSION}.so")
 SLBFGS_DP_REPLICATED, SLBFGS_DP_SLICED = 0, 1
+HVP_MODES = {"fd": 0, "exact": 1, "gauss_newton": 2}  # LBF_HVP_FD, LBF_HVP_EXACT, LBF_HVP_GAUSS_NEWTON
 LS_WOLFE, LS_ARMIJO = 0, 1
 INIT_CPU, INIT_CUDA = 0, 1
 ACTS = {"linear": 0, "tanh": 1, "relu": 2, "sigmoid": 3}
@@ -136,6 +137,7 @@ def lib():
         "lbf_idx_read_images": (C.c_int, [C.c_char_p, C.c_longlong, _vp, C.POINTER(C.c_longlong), _ip, _ip]),
         "lbf_idx_read_labels": (C.c_int, [C.c_char_p, C.c_longlong, C.c_int, _vp, C.POINTER(C.c_longlong)]),
         "lbf_mlp_hvp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_double, _vp]),
+        "lbf_mlp_gnvp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_double, _vp]),
         "lbf_mlp_loss": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, _dp]),
         "lbf_mlp_fd_hvp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_double,
                                      C.c_double, _vp]),
@@ -170,7 +172,7 @@ EXPORTS = ("lbf_last_error lbf_version lbf_abi_version lbf_ctx_create lbf_ctx_de
            "lbf_lbfgs_begin lbf_lbfgs_iterate lbf_lbfgs_end lbf_lbfgs_solve_fn lbf_device_alloc lbf_device_free lbf_memcpy lbf_slbfgs_solve lbf_slbfgs_begin lbf_slbfgs_iterate lbf_slbfgs_end lbf_slbfgs_pair0 lbf_slbfgs_pair_io lbf_prof_enable lbf_prof_select lbf_prof_sample lbf_prof_read lbf_prof_read_work lbf_synth_mnist "
            "lbf_sample_indices lbf_synth_regression lbf_gd_default_params lbf_sgd_default_params lbf_gd_solve "
            "lbf_sgd_solve lbf_idx_read_images lbf_idx_read_labels lbf_mlp_hvp lbf_mlp_fd_hvp lbf_mlp_loss "
-           "lbf_mlp_set_loss lbf_mlp_get_loss lbf_mlp_set_l2 lbf_mlp_get_l2 lbf_mlp_evaluate").split()
+           "lbf_mlp_set_loss lbf_mlp_get_loss lbf_mlp_set_l2 lbf_mlp_get_l2 lbf_mlp_evaluate lbf_mlp_gnvp").split()
 
 
 def check_l2(l2) -> float:

@@ -282,6 +282,16 @@ int lbf_mlp_hvp(lbf_mlp *net, const float *d_params, const float *d_v, const flo
   });
 }
 
+int lbf_mlp_gnvp(lbf_mlp *net, const float *d_params, const float *d_v, const float *d_X, const float *d_Y,
+                 const int *d_idx, long long batch, double inv_scale, double l2, float *d_gv) {
+  return guard([&] {
+    LBF_REQUIRE(net && d_params && d_v && d_gv && batch >= 0 && (batch == 0 || (d_X && d_Y)), "bad argument");
+    net->ctx->c.set_device();
+    net->net->gnvp(d_params, d_v, d_X, d_Y, d_idx, batch, inv_scale, l2, d_gv);
+    LBF_HIP(hipStreamSynchronize(net->ctx->c.stream));
+  });
+}
+
 int lbf_mlp_set_loss(lbf_mlp *net, int loss) {
   return guard([&] {
     LBF_REQUIRE(net, "null argument");

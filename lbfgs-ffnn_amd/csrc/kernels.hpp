@@ -271,6 +271,15 @@ void rop_out_xent(hipStream_t s, long long B, int Out, const float *Z, const flo
 void rop_back(hipStream_t s, long long n, const float *T1, const float *T2, const float *delta, const float *A,
               const float *RZ, int act, float *out);
 bool act_has_d2(int act);
+// Gauss-Newton product, elementwise steps (hvp.hip; products in Mlp::gnvp). R{Z} = T0 + T1 is formed inside each
+// launch and not stored; T1 null: no second product (layer 0).
+void gn_act(hipStream_t s, long long n, const float *A, const float *T0, const float *T1, int act, float *RA);
+// LOSS_MSE: M = s act'(A)^2 .* (T0 + T1) (no targets needed)
+void gn_out_mse(hipStream_t s, long long n, const float *A, const float *T0, const float *T1, int act,
+                double inv_scale, float *M);
+// LOSS_XENT: rop_out_xent on RZ = T0 + T1 (one wave per row)
+void gn_out_xent(hipStream_t s, long long B, int Out, const float *Z, const float *Y, const int *idx, const float *T0,
+                 const float *T1, double inv_scale, float *M);
 
 // BASELINE config 5's synthetic regression data on the device (synth.hip).
 void synth_regression(hipStream_t s, long long row0, long long N, int In, unsigned seed_x, unsigned seed_t, float *X,

@@ -179,6 +179,12 @@ public:
   // R-operator (hvp.hip); with a communicator the shards' products are all-reduced. Hv: nparams().
   void hvp(const float *P, const float *V, const float *X, const float *Y, const int *idx, long long B,
            double inv_scale, double lambda, float *Hv);
+  // Gauss-Newton vector product Gv = J^T H_L J V (+ lambda V) of the same batch loss (hvp.hip): positive
+  // semi-definite, no second-order terms. The loss is split from the network at the outputs A_L for the squared
+  // error (H_L = inv_scale I) and at the logits for the cross-entropy. Arguments, empty batch and all-reduce as
+  // hvp; it shares hvp's workspace, and the two may be called in any order with any batch sizes.
+  void gnvp(const float *P, const float *V, const float *X, const float *Y, const int *idx, long long B,
+            double inv_scale, double lambda, float *Gv);
   // Device-side evaluation (metrics.hip; replaces the host scan of unified_launcher.hpp:154-199): forward() and
   // the metrics kernel per chunk of chunk_rows rows (0: 65536, or the batch if smaller), so the activation
   // workspace is bounded by the chunk. Every chunk runs the forward plan of the whole batch, so the outputs, and
@@ -248,10 +254,17 @@ private:
   int dx_tile(long long B, int N) const;
   DevBuf<double> loss_part_, dots_part_, sse_, colpart_, trows_, tdots_;
   DevBuf<unsigned> cols_done_; // tail_cols arrival counter (zero between launches)
-  // R-pass workspace (hvp): R{Z}, R{A}, R{dZ} and delta per layer, two products, one segment
+  // R-pass workspace (hvp, gnvp): R{Z}, R{A}, R{dZ} and delta per layer, two products, one segment
   std::vector<DevBuf<float>> RZ_, RA_, RD_, DL_;
   DevBuf<float> T1_, T2_, seg_;
   long long rcap_ = -1;
+  void rpass_ensure(long long B); // grows the workspace to B rows
+  // the R-pass products of layer l on B rows, with the forward, dW and dX plans of ensure(B)
+  void rpass_linear_fwd(long long B, int l, const float *Wsrc, const float *in, const int *rows, bool with_bias,
+                        float *out);
+  void rpass_weight_grad(long long B, int l, const float *in, const int *rows, bool ones, const float *dZ,
+                         float *dst);
+  void rpass_back_prod(long long B, int l, const float *dZ, const float *Wsrc, int aux_act, float *out);
   // evaluate(): per-workgroup loss partials and counts [rows, correct, topk] of every chunk, the confusion cells,
   // the partials' sum, the all-reduce words
   DevBuf<double> ev_part_, ev_sum_;

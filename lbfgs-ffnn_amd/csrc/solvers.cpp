@@ -1035,9 +1035,13 @@ void SlbfgsSolver::epoch_steps(const EpochDraw &d) {
         pa.sa = u_.get();
         pa.sb = up_.get();
         float *gp = fdpair_.get(), *gm = fdpair_.get() + ng_;
-        if (prm_.hvp_exact) { // y = H(u) s on the b_H batch, R-operator (hvp.hip)
-          net_->hvp(u_.get(), s_.get(), X_, Y_, idx_.get() + hs.off, hs.cnt, 1.0 / double(hs.total), prm_.lambda,
-                    gp);
+        if (prm_.hvp_exact) { // y = H(u) s on the b_H batch, R-operator, or the Gauss-Newton G(u) s (hvp.hip)
+          if (prm_.hvp_exact == LBF_HVP_GAUSS_NEWTON)
+            net_->gnvp(u_.get(), s_.get(), X_, Y_, idx_.get() + hs.off, hs.cnt, 1.0 / double(hs.total), prm_.lambda,
+                       gp);
+          else
+            net_->hvp(u_.get(), s_.get(), X_, Y_, idx_.get() + hs.off, hs.cnt, 1.0 / double(hs.total), prm_.lambda,
+                      gp);
           LBF_HIP(hipMemsetAsync(gm, 0, size_t(n_) * sizeof(float), s));
           pa.yscale = 1.0;
         } else { // s_lbfgs.hpp:88-101: central difference of two batch gradients

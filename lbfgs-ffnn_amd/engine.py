@@ -14,7 +14,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import (ACTS, INIT_CPU, INIT_CUDA, LOSSES, check_l2, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED, SLBFGS_DP_SLICED,
+from ._lib import (ACTS, HVP_MODES, INIT_CPU, INIT_CUDA, LOSSES, check_l2, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED, SLBFGS_DP_SLICED,
                    EvalResultC, GdParams, LbfError, LbfgsParams, Record, SgdParams, SlbfgsParams, SolveInfo, check, lib,
                    ptr)
 
@@ -327,6 +327,21 @@ class Mlp:
                                 B, inv_scale, l2, ptr(out, numel=n)), "lbf_mlp_hvp")
         return out
 
+    def gnvp(self, params: torch.Tensor, v: torch.Tensor, X: torch.Tensor, Y: torch.Tensor,
+             idx: Optional[torch.Tensor] = None, inv_scale: Optional[float] = None, l2: float = 0.0,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Gauss-Newton product G(params) v + l2 v of the loss_grad batch loss (lbf_mlp_gnvp): G = J^T H_L J,
+        positive semi-definite, split at the outputs for "mse" and at the logits for "softmax_xent"."""
+        B = int(idx.numel()) if idx is not None else int(X.shape[0])
+        if inv_scale is None:
+            inv_scale = 1.0 / max(B, 1)
+        out = self.new_params() if out is None else out
+        self._check_data(X, Y)
+        n = self.nparams
+        check(lib().lbf_mlp_gnvp(self.h, ptr(params, numel=n), ptr(v, numel=n), ptr(X), ptr(Y), ptr(idx, torch.int32),
+                                 B, inv_scale, l2, ptr(out, numel=n)), "lbf_mlp_gnvp")
+        return out
+
     def fd_hvp(self, params: torch.Tensor, v: torch.Tensor, X: torch.Tensor, Y: torch.Tensor,
                idx: Optional[torch.Tensor] = None, inv_scale: Optional[float] = None, l2: float = 0.0,
                eps: float = 1e-4, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -393,6 +408,10 @@ def slbfgs_params(**kw) -> SlbfgsParams:
     lib().lbf_slbfgs_default_params(C.byref(p))
     if isinstance(kw.get("dp_mode"), str):
         kw["dp_mode"] = {"replicated": SLBFGS_DP_REPLICATED, "sliced": SLBFGS_DP_SLICED}[kw["dp_mode"]]
+    if isinstance(kw.get("hvp_exact"), str):  # "fd", "exact" or "gauss_newton" (LBF_HVP_*); an int passes through
+        if kw["hvp_exact"] not in HVP_MODES:
+            raise LbfError(f"unknown curvature {kw['hvp_exact']!r}: expected one of {sorted(HVP_MODES)}")
+        kw["hvp_exact"] = HVP_MODES[kw["hvp_exact"]]
     for k, v in kw.items():
         if v is not None:
             setattr(p, "reg" if k == "lam" else k, v)
@@ -479,7 +498,8 @@ class LbfgsRun:
 
 
 def slbfgs_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, pair_trace: int = 0, **kw):
-    """S-LBFGS (SVRG + FD-HVP curvature pairs); X/Y hold all N rows on every rank. pair_trace > 0 records up
+    """S-LBFGS (SVRG + FD-HVP curvature pairs; hvp_exact="exact" / "gauss_newton" or 1 / 2 takes the pairs' y from
+    Mlp.hvp / Mlp.gnvp instead); X/Y hold all N rows on every rank. pair_trace > 0 records up
     to that many curvature-pair candidates (diagnostics, synchronous) into hist["pairs"]: rows of (epoch, t,
     y.s, s.s, y.y, accepted, live pairs, 0)."""
     p = slbfgs_params(**kw)
@@ -536,7 +556,8 @@ class SlbfgsRun:
 
     def pair_io(self, cap: int, record: bool = True, force: Optional[torch.Tensor] = None):
         """Teacher forcing of the curvature pairs (lbf_slbfgs_pair_io; call before iterate). Returns the record
-        tensor [cap, 4, ld] ([w_{t+1} | u | g(u + eps s) | g(u - eps s)] per curvature event) or None; `force`
+        tensor [cap, 4, ld] ([w_{t+1} | u | g(u + eps s) | g(u - eps s)] per curvature event; with hvp_exact 1 / 2
+        the third block is H(u) s + lam s / G(u) s + lam s and the fourth is zero) or None; `force`
         (same shape, e.g. another run's record) replaces u and the two gradients of each event."""
         n = int(self._keep[1].numel())
         ld = (n + 3) & ~3

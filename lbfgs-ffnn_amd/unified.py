@@ -50,6 +50,8 @@ class UnifiedConfig:
                                  # like UnifiedLauncher.setLoss, and it then stays the network's loss)
     l2: float = 0.0              # weight decay of UnifiedLBFGS / UnifiedGD / UnifiedSGD (HIP extension; train()
                                  # applies a non-zero value like UnifiedLauncher.setL2, and it then stays)
+    curvature: str = "fd"        # UnifiedSLBFGS's curvature pairs (HIP extension): "fd" (the reference's finite
+                                 # difference), "exact" (R-operator H s) or "gauss_newton" (G s, always y.s > 0)
     # Validation-monitored training (HIP extension; UnifiedLBFGS and UnifiedSLBFGS). eval_every > 0: the test split
     # is evaluated on the device at iteration 0, every eval_every iterations (epochs for S-LBFGS) and at the end.
     eval_every: int = 0          # 0: off (the unmonitored code path)
@@ -302,12 +304,13 @@ class UnifiedSLBFGS(UnifiedOptimizer):
             _check_monitored(config, data)
             run = engine.SlbfgsRun(net.mlp, net.params, data.x_full, data.y_full, record_cap=max(config.max_iters, 1),
                                    tol=config.tolerance, M=config.m_param, L=config.L_param, b=config.batch_size,
-                                   b_H=b_H, step=config.learning_rate, lam=1e-4, seed=123)
+                                   b_H=b_H, step=config.learning_rate, lam=1e-4, seed=123,
+                                   hvp_exact=config.curvature)
             return _monitored_run(self, net, data, config, run)
         hist, info = engine.slbfgs_solve(net.mlp, net.params, data.x_full, data.y_full, max_epochs=config.max_iters,
                                          tol=config.tolerance, M=config.m_param, L=config.L_param,
                                          b=config.batch_size, b_H=b_H, step=config.learning_rate, lam=1e-4,
-                                         seed=123)
+                                         seed=123, hvp_exact=config.curvature)
         rec = IterationRecorder()
         for i in range(len(hist["loss"])):
             rec.record(i, float(hist["loss"][i]), float(hist["grad_norm"][i]), float(hist["time_ms"][i]))
