@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 
 namespace lbf {
 
@@ -239,11 +240,15 @@ void Mlp::plan(long long B) {
     if (L.splits > 1) slab += size_t(L.splits) * size_t(L.in + 1) * L.out; // every layer keeps its own slabs
   }
   if (show_plan_) {
-    for (int l = 0; l < nl; ++l)
-      std::fprintf(stderr, "[lbf plan] B=%lld layer %d: dW tile %d splits %d k_chunk %d | fwd tile %d splits %d\n", B,
-                   l, layers_[l].dtile, layers_[l].splits, layers_[l].k_chunk, layers_[l].ftile, layers_[l].fsplits);
+    for (int l = 0; l < nl; ++l) {
+      std::fprintf(stderr, "[lbf plan] B=%lld layer %d: dW tile %d splits %d k_chunk %d | fwd tile %d splits %d", B, l,
+                   layers_[l].dtile, layers_[l].splits, layers_[l].k_chunk, layers_[l].ftile, layers_[l].fsplits);
+      if (l >= 1) std::fprintf(stderr, " | dX tile %d", dx_tile(B, layers_[l].in)); // layer 0 has no dX GEMM
+      std::fprintf(stderr, "\n");
+    }
     std::fprintf(stderr, "[lbf plan] B=%lld fold %d from column %d\n", B, fold_, fold_c0_);
   }
+  asum_shown_ = false;
   slab_.ensure(slab);
   fslab_.ensure(std::max<size_t>(fslab, 1));
   fslab2_.ensure(std::max<size_t>(fslab, 1)); // odd layers' slabs: the next layer may read the previous one's
@@ -363,10 +368,12 @@ const float *Mlp::forward(const float *P, const float *X, const int *idx, long l
   const float *in = X;
   const size_t nr = nrun < 0 ? layers_.size() : size_t(nrun);
   bool pending = false; // layer l - 1's slabs are reduced by layer l's GEMM (its A prologue)
+  std::string asum; // LBF_SHOW_PLAN: the layers whose GEMM takes its A from slabs
   for (size_t l = 0; l < nr; ++l) {
     const Layer &L = layers_[l];
     GemmDesc d = fwd_launch_desc(l, P, in, idx, B);
     if (pending) set_asum(d, l - 1, P, B);
+    if (pending && show_plan_) asum += " " + std::to_string(l);
     {
       ProfScope ps(ctx_, PK_FWD, int(l), double(B));
       gemm(s, d);
@@ -386,6 +393,11 @@ const float *Mlp::forward(const float *P, const float *X, const int *idx, long l
         fwd_reduce_act(s, fslab_buf(l), L.fsplits, B * L.out, int(B), L.out, d.bias, L.act, A_[l].get(), ctx_->abort);
     }
     in = A_[l].get();
+  }
+  if (show_plan_ && !asum_shown_) { // once per plan, by the first forward that runs it
+    std::fprintf(stderr, "[lbf plan] B=%lld forward of %zu layers: A from slabs at layers%s\n", planned_, nr,
+                 asum.empty() ? " none" : asum.c_str());
+    asum_shown_ = true;
   }
   return in;
 }

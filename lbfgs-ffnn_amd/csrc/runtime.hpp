@@ -245,6 +245,7 @@ private:
   const bool group_dw_;  // dW of layers 1 and 0 in one launch (Switches::group_dw)
   const bool fold_on_;   // fold into the EPI_HEAD epilogue (Switches::fold; off: the unfolded route, tests)
   const bool show_plan_; // plan() reports each plan on stderr
+  bool asum_shown_ = false; // forward() has reported the current plan's A-from-slabs layers
   bool rowhead_on(long long B) const; // the standalone head fed by the last hidden layer's slabs
   // Planned fold: the last hidden layer's [dW ; db] rows fold_c0_ .. in (fold_ input columns and the
   // bias row) are computed in the forward GEMM's EPI_HEAD epilogue instead of a mostly empty last

@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 import torch
 
+from plan_report import T128, lost_route, on_plan_device, planned_layers
+
 pytestmark = pytest.mark.gpu
 
 CFG5 = ([4096, 2048, 1024, 1], ["relu", "relu", "linear"])
@@ -96,18 +98,26 @@ def test_cfg5_loss_grad_matches_oracle(ctx, pkg, O):
     assert rel(host(g), g_ref) <= max(1e-4, 3.0 * rel(g32, g_ref))
 
 
-def test_cfg5_loss_grad_split_plan_matches_oracle(ctx, pkg, O):
+def test_cfg5_loss_grad_split_plan_matches_oracle(ctx, pkg, O, monkeypatch, capfd):
     """cfg 5 against the fp64 oracle where the N = 1,000,000 route engages: from ~8k rows the
     two wide dW GEMMs run the 1M plan's 128 x 128 tiles with the same split counts (layer 0: 33 x 16 = 528 tiles
     in 29 splits, layer 1: 17 x 8 in 15; LBF_SHOW_PLAN output in profiles/r06/), the forward GEMMs run unsplit
     128-row tiles, and the last layer's 1024 x 1 dW is split many ways; below 2048 rows (the N <= 128 tests above)
-    every dW GEMM takes the small-batch 64 x 64 plan instead. Loss 1e-5, gradient 1e-4 (the full-size bounds)."""
+    every dW GEMM takes the small-batch 64 x 64 plan instead. Loss 1e-5, gradient 1e-4 (the full-size bounds).
+    The plan named here is read from the LBF_SHOW_PLAN report and asserted on 256 CUs."""
     dims, acts = CFG5
     N = 8192
     X, Y = pkg.synth_regression(ctx, N, dims[0])
+    monkeypatch.setenv("LBF_SHOW_PLAN", "1")
+    capfd.readouterr()
     net = pkg.Mlp(ctx, dims, acts)
     P = net.init_params(123, "cpu")
     loss, g = net.loss_grad(P, X, Y)
+    plan = planned_layers(capfd.readouterr().err, N, 3)
+    got = ([p[0] for p in plan[:2]], [p[1][:2] for p in plan[:2]], plan[2][1][1] > 1)  # fwd, dW (tile, splits); last split
+    want = ([(T128, 1), (T128, 1)], [(T128, 29), (T128, 15)], True)
+    if on_plan_device():
+        assert got == want, lost_route(f"cfg 5 at {N} rows", got, want)
     onet = O.Net(dims, acts)
     l_ref, g_ref = onet.loss_grad(host(P), host(X), host(Y))
     e = rel(host(g), g_ref)

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from plan_report import T32x128, T64x128, lost_route, on_plan_device, planned_layers
+
 pytestmark = pytest.mark.gpu
 
 LOSS_RTOL = 1e-5
@@ -97,16 +99,23 @@ def test_loss_grad_gather_and_l2(ctx, pkg, O):
                                        ([784, 128, 64, 10], ["relu", "relu", "linear"])])
 @pytest.mark.parametrize("N,gather", [(8192, False), (8200, False), (15000, True), (30000, False),
                                       (32768, False), (32800, True)])
-def test_forward_tile_routes_match_oracle(ctx, pkg, O, dims, acts, N, gather):
+def test_forward_tile_routes_match_oracle(ctx, pkg, O, monkeypatch, capfd, dims, acts, N, gather):
     """Mlp::plan's forward row tiles at a rank's shard sizes (its cost model picks 32 x 128 at 8192 rows,
     64 x 128 at 8200 / 15000 / 30000 / 32768 / 32800 on 256 CUs; 128 x 128 at 60000 elsewhere); each with
-    the fused head and the fold, against the oracle (gathered rows: the S-LBFGS anchor path)."""
+    the fused head and the fold, against the oracle (gathered rows: the S-LBFGS anchor path). The 784 -> 128
+    layer's tile is read from the LBF_SHOW_PLAN report and asserted on 256 CUs."""
     Xh, Yh = pkg.synth_mnist(N, dims[0], dims[-1], 7)
     idx = np.random.default_rng(N).permutation(N)[: N - 37].astype(np.int64) if gather else None
+    monkeypatch.setenv("LBF_SHOW_PLAN", "1")
+    capfd.readouterr()
     net = pkg.Mlp(ctx, dims, acts)
     P = net.init_params(123, "cpu")
     loss, g = net.loss_grad(P, dev(Xh), dev(Yh),
                             idx=torch.from_numpy(idx.astype(np.int32)).cuda() if gather else None)
+    fwd0 = planned_layers(capfd.readouterr().err, N - 37 if gather else N, len(acts))[0][0]
+    want = (T32x128 if N == 8192 else T64x128, 1)
+    if on_plan_device():
+        assert fwd0 == want, lost_route(f"{dims} at {N} rows", fwd0, want)
     l_ref, g_ref = O.Net(dims, acts).loss_grad(host(P), Xh.astype(np.float64), Yh.astype(np.float64), idx=idx)
     assert abs(loss - l_ref) <= LOSS_RTOL * abs(l_ref)
     assert rel(host(g), g_ref) <= GRAD_RTOL
