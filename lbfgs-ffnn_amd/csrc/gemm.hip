@@ -21,6 +21,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace lbf {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -860,6 +862,87 @@ __device__ __forceinline__ void glds_body(const GemmK &g, float *lds, int zsplit
     lds_frag(buf, f);
     mfma_frag(f);
   };
+  // The 128 x 128 tile (four waves, NS = 2) runs a software-pipelined loop over half k-tiles: half h holds
+  // k-steps [8h, 8h + 8) of every (tm, tn) operand (quads 2h, 2h + 1 of a k-contiguous lane's 16 floats), so
+  // a wave's LDS reads are issued under its own MFMAs instead of in front of them.
+  constexpr bool PIPE = KW == 1 && TM == 2 && TN == 2 && NS == 2 && !ASUM;
+  constexpr int HK = 8;                                   // k-steps per half
+  constexpr int NRH = (AKC ? 4 : 16) + (BKC ? 4 : 16);    // LDS reads per half (TM = TN = 2)
+  constexpr int NMH = HK * TM * TN;                       // MFMAs per half
+  struct FragH {
+    float a[TM][HK], b[TN][HK];
+  };
+  auto lds_half = [&](int buf, int h, FragH &f) {
+    const float *As = lds + buf * STG;
+    const float *Bs = As + ASZ;
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm) {
+      const int row = wm * TM * 32 + tm * 32 + li;
+      if constexpr (AKC) {
+        const int sw = (row >> 1) & 7;
+#pragma unroll
+        for (int qq = 0; qq < 2; ++qq) {
+          const f32x4 v = *reinterpret_cast<const f32x4 *>(As + row * BK + 4 * ((lh * 4 + 2 * h + qq) ^ sw));
+#pragma unroll
+          for (int e = 0; e < 4; ++e) f.a[tm][qq * 4 + e] = v[e];
+        }
+      } else {
+#pragma unroll
+        for (int ss = 0; ss < HK; ++ss) f.a[tm][ss] = As[(lh * 16 + h * HK + ss) * BM + (row ^ (lh << 5))];
+      }
+    }
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) {
+      const int row = wn * TN * 32 + tn * 32 + li;
+      if constexpr (BKC) {
+        const int sw = (row >> 1) & 7;
+#pragma unroll
+        for (int qq = 0; qq < 2; ++qq) {
+          const f32x4 v = *reinterpret_cast<const f32x4 *>(Bs + row * BK + 4 * ((lh * 4 + 2 * h + qq) ^ sw));
+#pragma unroll
+          for (int e = 0; e < 4; ++e) f.b[tn][qq * 4 + e] = v[e];
+        }
+      } else {
+#pragma unroll
+        for (int ss = 0; ss < HK; ++ss) f.b[tn][ss] = Bs[(lh * 16 + h * HK + ss) * BN + (row ^ (lh << 5))];
+      }
+    }
+  };
+  auto mfma_half = [&](const FragH &f) { // mfma_frag's order: ss, then tm, then tn
+#pragma unroll
+    for (int ss = 0; ss < HK; ++ss)
+#pragma unroll
+      for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn)
+          acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[tm][ss], f.b[tn][ss], acc[tm][tn], 0, 0, 0);
+  };
+  // Reads half h of buffer buf into dst under the MFMAs of src (in registers): one MFMA first, then the DMA
+  // pieces of k-tile dma_t (DMA) and the LDS reads dealt between the next MFMAs, the rest behind them.
+  auto read_under = [&](int buf, int h, FragH &dst, const FragH &src, auto dma_c, int dma_t) {
+    constexpr bool DMA = decltype(dma_c)::value;
+    constexpr int MFMA = 0x8, VMEM = 0x10, DSRD = 0x100;
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (DMA) issue(dma_t);
+    lds_half(buf, h, dst);
+    mfma_half(src);
+    __builtin_amdgcn_sched_group_barrier(MFMA, 1, 0);
+    if constexpr (DMA) {
+#pragma unroll
+      for (int r = 0; r < P; ++r) {
+        __builtin_amdgcn_sched_group_barrier(VMEM, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(MFMA, 1, 0);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < NRH; r += 2) {
+      __builtin_amdgcn_sched_group_barrier(DSRD, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(MFMA, 1, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(MFMA, NMH - 1 - (DMA ? P : 0) - NRH / 2, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  static_assert(!PIPE || NMH - 1 - P - NRH / 2 >= 0, "MFMAs to interleave with");
 
   if (epi_head(EPI)) KT(0);
   if (epi_head(EPI)) KTC(40);
@@ -905,10 +988,41 @@ __device__ __forceinline__ void glds_body(const GemmK &g, float *lds, int zsplit
       if (ok && bx == 0) *reinterpret_cast<f32x4 *>(g.a_out + rbase + kq) = a4;
     }
   }
+  if constexpr (PIPE) {
+    // f0 / f1 hold half 0 / half 1 of a k-tile. A pass runs k-tile i's second half and k-tile i + 1's first:
+    // behind the barrier every wave has k-tile i + 1 landed and its reads of k-tile i done (lgkmcnt(0)), so
+    // buffer i % 2 takes k-tile i + 2, which has a whole k-tile to land. nk barriers for every nk
+    // (block-uniform), as the plain loop below: one here, one per pass. The last pass has no DMA and is
+    // peeled, so that every pass is straight-line code.
+    if (nk > 0) {
+      const std::true_type yes;
+      const std::false_type no;
+      FragH f0, f1;
+      issue(0);
+      vm_wait<0>();
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      if (epi_head(EPI)) KT(1);
+      if (1 < nk) issue(1);
+      lds_half(0, 0, f0);
+      read_under(0, 1, f1, f0, no, 0);
+      auto pass = [&](int i, auto dma_c) {
+        vm_wait<0>(); // this wave's pieces of k-tile i + 1 landed
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        if (epi_head(EPI) && i + 1 < 24) KT(2 + i);
+        read_under((i + 1) & 1, 0, f0, f1, dma_c, i + 2);
+        read_under((i + 1) & 1, 1, f1, f0, no, 0);
+      };
+      for (int i = 0; i + 2 < nk; ++i) pass(i, yes);
+      if (nk >= 2) pass(nk - 2, no);
+      __builtin_amdgcn_sched_barrier(0);
+      mfma_half(f1);
+    }
+  } else {
 #pragma unroll
-  for (int t = 0; t < NS - 1; ++t)
-    if (t < nk) issue(t);
-  {
+    for (int t = 0; t < NS - 1; ++t)
+      if (t < nk) issue(t);
     for (int i = 0; i < nk; ++i) {
       vm_wait_tiles<PD, NS>(min(NS - 2, nk - 1 - i)); // this wave's pieces of k-tile i landed
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
