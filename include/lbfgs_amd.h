@@ -346,6 +346,74 @@ int lbf_gd_solve(lbf_mlp *net, const lbf_gd_params *prm, float *d_params, const 
 int lbf_sgd_solve(lbf_mlp *net, const lbf_sgd_params *prm, float *d_params, const float *d_X, const float *d_Y,
                   long long N, lbf_record *rec, lbf_solve_info *info);
 
+/* ---- Hessian-free (truncated Newton) optimisation: Gauss-Newton conjugate gradients (extension; Martens 2010).
+ * New functions and structs only: LBF_ABI_VERSION stays 3.
+ *
+ * lbf_mlp_gn_cg solves (G + damping I) x = b by conjugate gradients from x = 0, G the Gauss-Newton matrix of
+ * lbf_mlp_gnvp at d_params on the given batch (same d_idx / batch / inv_scale meaning, shards summed over a
+ * communicator, batch == 0 an empty share). The forward pass runs once for the whole solve; an iteration is the
+ * product on the direction plus three sweeps over the parameters, and every scalar (alpha, beta, the stopping
+ * test) is formed on the device from fixed-order fp64 partial sums: no host round trip per iteration, no float
+ * atomics, bitwise reproducible. The host enqueues `check` iterations, then reads the status block; launches
+ * enqueued past the stopping iteration are no-ops, so the result does not depend on `check`.
+ *   status 0: rr <= rtol^2 rr0 (b = 0 gives x = 0 in 0 iterations);  1: max_iters reached;
+ *          2: p.Ap <= 0 or non-finite (an indefinite damping, a non-finite input): that iteration's update is not
+ *             applied and x is the last good iterate.
+ * rr0 = b.b, rr = r.r of the recurrence residual, xb = x.b, xr = x.r, xx = x.x (fp64). d_x and d_b: parameter
+ * count floats, 4-byte aligned. LBF_ERR_INVALID: null handles, max_iters < 0, rtol < 0, check < 1. */
+typedef struct lbf_cg_params {
+  int max_iters;  /* 50  */
+  double rtol;    /* 0.1: stop when ||r|| <= rtol ||b|| */
+  double damping; /* 0   */
+  int check;      /* 10: iterations enqueued between two reads of the status block */
+} lbf_cg_params;
+typedef struct lbf_cg_info {
+  int iterations, status;
+  double rr0, rr, xb, xr, xx;
+} lbf_cg_info;
+void lbf_cg_default_params(lbf_cg_params *p);
+int lbf_mlp_gn_cg(lbf_mlp *net, const float *d_params, const float *d_b, const float *d_X, const float *d_Y,
+                  const int *d_idx, long long batch, double inv_scale, const lbf_cg_params *prm, float *d_x,
+                  lbf_cg_info *info);
+/* Diagnostics: the recurrence residual r of the network's last lbf_mlp_gn_cg / Hessian-free step (parameter count
+ * floats into a device buffer). LBF_ERR_INVALID before the first solve. */
+int lbf_mlp_gn_cg_residual(lbf_mlp *net, float *d_r);
+
+/* Hessian-free solver on the objective of lbf_gd_solve (the network's loss + its l2, a mean over n_global, n_local
+ * rows on this rank). Outer iteration k, with damping lambda_k (lambda_0 = damping0):
+ *   1. f, g by the fused evaluation; stop when ||g|| < tol;
+ *   2. CG on (G + (l2 + lambda_k) I) p = -g, at most cg_iters iterations, relative residual cg_rtol;
+ *   3. model value q = g.p + 0.5 p^T (G + l2 I) p, from the CG status block;
+ *   4. backtracking: alpha = 1, rho, rho^2, .. (at most max_line_iters trials, loss-only evaluations) until
+ *      f(x + alpha p) <= f + c1 alpha g.p; if every trial fails the point stays (accepted = 0, alpha = 0);
+ *   5. ratio = (f(x + p) - f) / q from the first trial; lambda *= damp_up if ratio < ratio_lo, lambda *= damp_down
+ *      if ratio > ratio_hi;
+ *   6. lbf_record row: loss and gradient norm at the iteration's start point, alpha, ls_trials, accepted.
+ * curv_rows > 0: the curvature (step 2) is taken on the contiguous window of curv_rows rows starting at
+ * (k curv_rows) mod (n_local - curv_rows + 1), with inv_scale 1 / curv_rows; single rank only (LBF_ERR_INVALID
+ * with a communicator, like lbf_sgd_solve). curv_rows == 0: all local rows; with a communicator every rank then
+ * runs the same vector arithmetic on all-reduced inputs and takes the same decisions.
+ * Traces (nullable, trace_cap entries): per outer iteration the damping after step 5, the ratio, the CG
+ * iterations. info->n_evals counts the fused evaluations (one per outer iteration and the final point's),
+ * n_loss_only the line-search trials. */
+typedef struct lbf_hf_params {
+  int max_iters;      /* outer iterations, 100 */
+  double tol;         /* stop when ||g|| < tol, 1e-6 */
+  int cg_iters;       /* 50  */
+  double cg_rtol;     /* 0.1 */
+  int cg_check;       /* 10  */
+  double damping0, damp_up, damp_down, ratio_lo, ratio_hi; /* 1.0, 1.5, 2/3, 0.25, 0.75 */
+  double c1, rho;     /* 1e-4, 0.5 */
+  int max_line_iters; /* 20 */
+  long long curv_rows; /* 0: all local rows */
+  double *damping_trace, *ratio_trace;
+  int *cg_trace;
+  int trace_cap;
+} lbf_hf_params;
+void lbf_hf_default_params(lbf_hf_params *p);
+int lbf_hf_solve(lbf_mlp *net, const lbf_hf_params *prm, float *d_params, const float *d_X, const float *d_Y,
+                 long long n_local, long long n_global, lbf_record *rec, lbf_solve_info *info);
+
 int lbf_slbfgs_solve(lbf_mlp *net, const lbf_slbfgs_params *prm, float *d_params, const float *d_X,
                      const float *d_Y, long long N, lbf_record *rec, lbf_solve_info *info);
 /* Stateful S-LBFGS (benchmarking, and callers that check progress between epochs): begin copies nothing

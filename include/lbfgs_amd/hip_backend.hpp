@@ -354,6 +354,57 @@ private:
   int ls_ = LBF_LS_ARMIJO;
 };
 
+/// Hessian-free (truncated Newton) minimizer on a HipNetwork (HIP extension, no reference counterpart:
+/// lbf_hf_solve, Gauss-Newton CG steps with Levenberg-Marquardt damping). The curvature needs the network, not
+/// only its loss and gradient, so solve() minimises the network's own loss (+ its l2) on input / target and does
+/// not call loss_grad; n must be the network's parameter count.
+class HipHF : public HipMinimizerBase {
+public:
+  HipHF(HipHandle &handle, HipNetwork &net) : HipMinimizerBase(handle), net_(net) {}
+  void setCG(int iters, double rtol) {
+    cg_iters_ = iters;
+    cg_rtol_ = rtol;
+  }
+  void setDamping(double damping0) { damping0_ = damping0; }
+  void setCurvatureRows(long long rows) { curv_rows_ = rows; }
+
+  void solve(int n, HipScalar *params, const HipScalar *input, const HipScalar *target, int batch,
+             const LossGradFun &) override {
+    if (n <= 0 || params == nullptr) {
+      last_iterations_ = 0;
+      return;
+    }
+    lbf_hf_params prm;
+    lbf_hf_default_params(&prm);
+    prm.max_iters = max_iters_;
+    prm.tol = tol_;
+    prm.cg_iters = cg_iters_;
+    prm.cg_rtol = cg_rtol_;
+    prm.damping0 = damping0_;
+    prm.curv_rows = curv_rows_;
+    prm.max_line_iters = max_line_iters_;
+    prm.c1 = c1_;
+    prm.rho = rho_;
+    lbf_record rec{};
+    lbf_record *rp = nullptr;
+    if (recorder_) {
+      recorder_->reset();
+      rec = recorder_->view();
+      rp = &rec;
+    }
+    lbf_solve_info info{};
+    hip_check(lbf_hf_solve(net_.raw(), &prm, params, input, target, batch, batch, rp, &info), "lbf_hf_solve");
+    if (recorder_) recorder_->set_size(rec.size);
+    last_iterations_ = info.iterations;
+  }
+
+private:
+  HipNetwork &net_;
+  int cg_iters_ = 50;
+  double cg_rtol_ = 0.1, damping0_ = 1.0;
+  long long curv_rows_ = 0;
+};
+
 /// Column-major host matrix with the subset of Eigen::MatrixXd's interface the launcher uses.
 class HostMatrix {
 public:
@@ -419,6 +470,10 @@ struct UnifiedConfig {
   /// HIP extension: UnifiedSLBFGS_HIP's curvature pairs, LBF_HVP_FD (the reference's finite difference),
   /// LBF_HVP_EXACT or LBF_HVP_GAUSS_NEWTON (lbf_slbfgs_params.hvp_exact)
   int curvature = LBF_HVP_FD;
+  /// HIP extension: UnifiedHF_HIP's CG iterations and relative residual per step and its initial damping
+  int cg_iters = 50;
+  double cg_rtol = 0.1;
+  double damping = 1.0;
 };
 /// src/unified_optimization.hpp:54-59 (HostMatrix instead of Eigen::MatrixXd)
 struct UnifiedDataset {
@@ -553,6 +608,35 @@ public:
     hip_mlp::hip_check(lbf_gd_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n_train, n_train, &rec,
                                     &info),
                        "lbf_gd_solve");
+    recorder.set_size(rec.size);
+    write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
+  }
+};
+
+/// Hessian-free training (HIP extension, no reference counterpart): lbf_hf_solve with the config's max_iters and
+/// tolerance and, where the config is this header's own, its cg_iters, cg_rtol and damping.
+class UnifiedHF_HIP : public UnifiedOptimizer<HipBackend> {
+public:
+  void optimize(hip_mlp::HipHandle &, NetworkWrapper<HipBackend> &net, const UnifiedDataset &host_data,
+                hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dx, hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dy,
+                const UnifiedConfig &c) override {
+    const long n_train = long(host_data.train_x.cols());
+    auto &nw = net.getInternal();
+    lbf_hf_params prm;
+    lbf_hf_default_params(&prm);
+    prm.max_iters = c.max_iters;
+    prm.tol = c.tolerance;
+#ifndef LBF_USE_REFERENCE_UNIFIED_TYPES // the reference's own UnifiedConfig has no such members
+    prm.cg_iters = c.cg_iters;
+    prm.cg_rtol = c.cg_rtol;
+    prm.damping0 = c.damping;
+#endif
+    recorder.init(c.max_iters);
+    lbf_record rec = recorder.view();
+    lbf_solve_info info{};
+    hip_mlp::hip_check(lbf_hf_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n_train, n_train, &rec,
+                                    &info),
+                       "lbf_hf_solve");
     recorder.set_size(rec.size);
     write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
   }

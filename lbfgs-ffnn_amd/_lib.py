@@ -49,6 +49,23 @@ class SgdParams(C.Structure):
                 ("decay_step", C.c_int), ("max_epochs", C.c_int), ("tol", C.c_double)]
 
 
+class CgParams(C.Structure):  # lbf_cg_params
+    _fields_ = [("max_iters", C.c_int), ("rtol", C.c_double), ("damping", C.c_double), ("check", C.c_int)]
+
+
+class CgInfo(C.Structure):  # lbf_cg_info
+    _fields_ = [("iterations", C.c_int), ("status", C.c_int), ("rr0", C.c_double), ("rr", C.c_double),
+                ("xb", C.c_double), ("xr", C.c_double), ("xx", C.c_double)]
+
+
+class HfParams(C.Structure):  # lbf_hf_params
+    _fields_ = [("max_iters", C.c_int), ("tol", C.c_double), ("cg_iters", C.c_int), ("cg_rtol", C.c_double),
+                ("cg_check", C.c_int), ("damping0", C.c_double), ("damp_up", C.c_double), ("damp_down", C.c_double),
+                ("ratio_lo", C.c_double), ("ratio_hi", C.c_double), ("c1", C.c_double), ("rho", C.c_double),
+                ("max_line_iters", C.c_int), ("curv_rows", C.c_longlong), ("damping_trace", C.POINTER(C.c_double)),
+                ("ratio_trace", C.POINTER(C.c_double)), ("cg_trace", C.POINTER(C.c_int)), ("trace_cap", C.c_int)]
+
+
 class Record(C.Structure):
     _fields_ = [("loss", C.POINTER(C.c_double)), ("grad_norm", C.POINTER(C.c_double)),
                 ("time_ms", C.POINTER(C.c_double)), ("alpha", C.POINTER(C.c_double)),
@@ -152,6 +169,13 @@ def lib():
         "lbf_mlp_get_loss": (C.c_int, [_vp, _ip]),
         "lbf_mlp_set_l2": (C.c_int, [_vp, C.c_double]),
         "lbf_mlp_get_l2": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+        "lbf_cg_default_params": (None, [C.POINTER(CgParams)]),
+        "lbf_mlp_gn_cg": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.POINTER(CgParams), _vp,
+                                    C.POINTER(CgInfo)]),
+        "lbf_mlp_gn_cg_residual": (C.c_int, [_vp, _vp]),
+        "lbf_hf_default_params": (None, [C.POINTER(HfParams)]),
+        "lbf_hf_solve": (C.c_int, [_vp, C.POINTER(HfParams), _vp, _vp, _vp, C.c_longlong, C.c_longlong,
+                                   C.POINTER(Record), C.POINTER(SolveInfo)]),
         "lbf_mlp_evaluate": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_int, C.c_longlong,
                                        C.POINTER(EvalResultC), _vp, _vp, _vp]),
     }
@@ -172,7 +196,8 @@ EXPORTS = ("lbf_last_error lbf_version lbf_abi_version lbf_ctx_create lbf_ctx_de
            "lbf_lbfgs_begin lbf_lbfgs_iterate lbf_lbfgs_end lbf_lbfgs_solve_fn lbf_device_alloc lbf_device_free lbf_memcpy lbf_slbfgs_solve lbf_slbfgs_begin lbf_slbfgs_iterate lbf_slbfgs_end lbf_slbfgs_pair0 lbf_slbfgs_pair_io lbf_prof_enable lbf_prof_select lbf_prof_sample lbf_prof_read lbf_prof_read_work lbf_synth_mnist "
            "lbf_sample_indices lbf_synth_regression lbf_gd_default_params lbf_sgd_default_params lbf_gd_solve "
            "lbf_sgd_solve lbf_idx_read_images lbf_idx_read_labels lbf_mlp_hvp lbf_mlp_fd_hvp lbf_mlp_loss "
-           "lbf_mlp_set_loss lbf_mlp_get_loss lbf_mlp_set_l2 lbf_mlp_get_l2 lbf_mlp_evaluate lbf_mlp_gnvp").split()
+           "lbf_mlp_set_loss lbf_mlp_get_loss lbf_mlp_set_l2 lbf_mlp_get_l2 lbf_mlp_evaluate lbf_mlp_gnvp "
+           "lbf_cg_default_params lbf_mlp_gn_cg lbf_mlp_gn_cg_residual lbf_hf_default_params lbf_hf_solve").split()
 
 
 def check_l2(l2) -> float:

@@ -516,6 +516,73 @@ int lbf_sgd_solve(lbf_mlp *net, const lbf_sgd_params *prm, float *d_params, cons
   });
 }
 
+void lbf_cg_default_params(lbf_cg_params *p) {
+  if (!p) return;
+  p->max_iters = 50;
+  p->rtol = 0.1;
+  p->damping = 0.0;
+  p->check = 10;
+}
+
+int lbf_mlp_gn_cg(lbf_mlp *net, const float *d_params, const float *d_b, const float *d_X, const float *d_Y,
+                  const int *d_idx, long long batch, double inv_scale, const lbf_cg_params *prm, float *d_x,
+                  lbf_cg_info *info) {
+  return guard([&] {
+    LBF_REQUIRE(net && prm && d_params && d_b && d_x && batch >= 0 && (batch == 0 || (d_X && d_Y)), "bad argument");
+    net->ctx->c.set_device();
+    Mlp::CgInfo ci;
+    net->net->gn_cg(d_params, d_b, 1.0f, d_X, d_Y, d_idx, batch, inv_scale, prm->damping, prm->max_iters, prm->rtol,
+                    prm->check, d_x, &ci);
+    if (info) {
+      info->iterations = ci.iterations;
+      info->status = ci.status;
+      info->rr0 = ci.rr0;
+      info->rr = ci.rr;
+      info->xb = ci.xb;
+      info->xr = ci.xr;
+      info->xx = ci.xx;
+    }
+  });
+}
+
+int lbf_mlp_gn_cg_residual(lbf_mlp *net, float *d_r) {
+  return guard([&] {
+    LBF_REQUIRE(net && d_r, "null argument");
+    LBF_REQUIRE(net->net->cg_residual(), "no conjugate-gradient solve has run on this network");
+    net->ctx->c.set_device();
+    hipStream_t s = net->ctx->c.stream;
+    LBF_HIP(hipMemcpyAsync(d_r, net->net->cg_residual(), net->net->nparams() * sizeof(float), hipMemcpyDeviceToDevice,
+                           s));
+    LBF_HIP(hipStreamSynchronize(s));
+  });
+}
+
+void lbf_hf_default_params(lbf_hf_params *p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->max_iters = 100;
+  p->tol = 1e-6;
+  p->cg_iters = 50;
+  p->cg_rtol = 0.1;
+  p->cg_check = 10;
+  p->damping0 = 1.0;
+  p->damp_up = 1.5;
+  p->damp_down = 2.0 / 3.0;
+  p->ratio_lo = 0.25;
+  p->ratio_hi = 0.75;
+  p->c1 = 1e-4;
+  p->rho = 0.5;
+  p->max_line_iters = 20;
+}
+
+int lbf_hf_solve(lbf_mlp *net, const lbf_hf_params *prm, float *d_params, const float *d_X, const float *d_Y,
+                 long long n_local, long long n_global, lbf_record *rec, lbf_solve_info *info) {
+  return guard([&] {
+    LBF_REQUIRE(net && prm, "null argument");
+    run_hf(net->net.get(), *prm, d_params, d_X, d_Y, n_local, n_global, rec, info);
+  });
+}
+
 void lbf_slbfgs_default_params(lbf_slbfgs_params *p) {
   if (!p) return;
   p->max_epochs = 1000; // stochastic_minimizer.hpp:44-47

@@ -104,7 +104,8 @@ __global__ __launch_bounds__(256) void rop_back_kernel(long long n, const float 
 
 // RA = act'(A) .* (T0 + T1)
 __global__ __launch_bounds__(256) void gn_act_kernel(long long n, const float *A, const float *T0, const float *T1,
-                                                     int act, float *RA) {
+                                                     int act, float *RA, const int *abort) {
+  if (abort && *abort) return;
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n) return;
   float rz = T0[e];
@@ -114,7 +115,9 @@ __global__ __launch_bounds__(256) void gn_act_kernel(long long n, const float *A
 
 // M = s act'(A)^2 .* (T0 + T1): the squared error's Hessian s I at the outputs A_L, pulled back to Z_L
 __global__ __launch_bounds__(256) void gn_out_mse_kernel(long long n, const float *A, const float *T0,
-                                                         const float *T1, int act, float s, float *M) {
+                                                         const float *T1, int act, float s, float *M,
+                                                         const int *abort) {
+  if (abort && *abort) return;
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n) return;
   float rz = T0[e];
@@ -127,7 +130,8 @@ __global__ __launch_bounds__(256) void gn_out_mse_kernel(long long n, const floa
 // arithmetic (the cross-entropy's Hessian at the logits is the whole second-order term of that loss)
 __global__ __launch_bounds__(256) void gn_out_xent_kernel(long long B, int Out, const float *Z, const float *Y,
                                                           const int *idx, const float *T0, const float *T1, float s,
-                                                          float *M) {
+                                                          float *M, const int *abort) {
+  if (abort && *abort) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (long long b = (long long)blockIdx.x * 4 + wave; b < B; b += (long long)gridDim.x * 4) { // wave-uniform
     const float *z = Z + b * Out, *t0 = T0 + b * Out, *t1 = T1 ? T1 + b * Out : nullptr;
@@ -153,25 +157,26 @@ __global__ __launch_bounds__(256) void gn_out_xent_kernel(long long B, int Out, 
 
 } // namespace
 
-void gn_act(hipStream_t s, long long n, const float *A, const float *T0, const float *T1, int act, float *RA) {
+void gn_act(hipStream_t s, long long n, const float *A, const float *T0, const float *T1, int act, float *RA,
+            const int *abort) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(gn_act_kernel, dim3(unsigned(cdiv(n, 256))), dim3(256), 0, s, n, A, T0, T1, act, RA);
+  hipLaunchKernelGGL(gn_act_kernel, dim3(unsigned(cdiv(n, 256))), dim3(256), 0, s, n, A, T0, T1, act, RA, abort);
   LBF_KERNEL_CHECK();
 }
 
 void gn_out_mse(hipStream_t s, long long n, const float *A, const float *T0, const float *T1, int act,
-                double inv_scale, float *M) {
+                double inv_scale, float *M, const int *abort) {
   if (n <= 0) return;
   hipLaunchKernelGGL(gn_out_mse_kernel, dim3(unsigned(cdiv(n, 256))), dim3(256), 0, s, n, A, T0, T1, act,
-                     float(inv_scale), M);
+                     float(inv_scale), M, abort);
   LBF_KERNEL_CHECK();
 }
 
 void gn_out_xent(hipStream_t s, long long B, int Out, const float *Z, const float *Y, const int *idx, const float *T0,
-                 const float *T1, double inv_scale, float *M) {
+                 const float *T1, double inv_scale, float *M, const int *abort) {
   if (B <= 0) return;
   hipLaunchKernelGGL(gn_out_xent_kernel, dim3(unsigned(std::min<long long>(cdiv(B, 4), 4096))), dim3(256), 0, s, B,
-                     Out, Z, Y, idx, T0, T1, float(inv_scale), M);
+                     Out, Z, Y, idx, T0, T1, float(inv_scale), M, abort);
   LBF_KERNEL_CHECK();
 }
 

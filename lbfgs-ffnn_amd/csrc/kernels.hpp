@@ -273,13 +273,48 @@ void rop_back(hipStream_t s, long long n, const float *T1, const float *T2, cons
 bool act_has_d2(int act);
 // Gauss-Newton product, elementwise steps (hvp.hip; products in Mlp::gnvp). R{Z} = T0 + T1 is formed inside each
 // launch and not stored; T1 null: no second product (layer 0).
-void gn_act(hipStream_t s, long long n, const float *A, const float *T0, const float *T1, int act, float *RA);
+// abort (nullable, all three and lincomb): the launch is a no-op when *abort != 0 (a frozen CG iteration, cg.hip)
+void gn_act(hipStream_t s, long long n, const float *A, const float *T0, const float *T1, int act, float *RA,
+            const int *abort = nullptr);
 // LOSS_MSE: M = s act'(A)^2 .* (T0 + T1) (no targets needed)
 void gn_out_mse(hipStream_t s, long long n, const float *A, const float *T0, const float *T1, int act,
-                double inv_scale, float *M);
+                double inv_scale, float *M, const int *abort = nullptr);
 // LOSS_XENT: rop_out_xent on RZ = T0 + T1 (one wave per row)
 void gn_out_xent(hipStream_t s, long long B, int Out, const float *Z, const float *Y, const int *idx, const float *T0,
-                 const float *T1, double inv_scale, float *M);
+                 const float *T1, double inv_scale, float *M, const int *abort = nullptr);
+
+// ------------------------------------------------------------------------------------------------
+// Device-side conjugate gradients on A x = b (cg.hip; the driver and A = G + damping I are Mlp::gn_cg). One
+// iteration is the product Ap followed by cg_pap, cg_step and cg_dir. Every scalar is an fp64 sum of
+// per-workgroup partials that each workgroup of the consuming launch re-derives in index order, so all of them
+// hold the same bits; no atomics, no waiting on another workgroup. The stopping decision is taken the same way
+// by every workgroup; workgroup 0 also writes the status block and raises the abort word, which turns every
+// launch already enqueued behind it into a no-op. A launch that decides to stop writes no vector, so whether
+// one of its workgroups sees the word or re-derives the decision makes no difference.
+// ------------------------------------------------------------------------------------------------
+enum { CG_ITER = 0, CG_RR = 1, CG_RR0 = 2, CG_STATUS = 3, CG_XB = 4, CG_XR = 5, CG_XX = 6, CG_N = 8 };
+enum { CG_RUNNING = -1, CG_CONVERGED = 0, CG_MAXITER = 1, CG_BREAKDOWN = 2 };
+int cg_nwg(long long n); // workgroups == partials per table: a function of n only
+struct CgArgs {
+  long long n = 0;
+  float *x = nullptr, *r = nullptr, *p = nullptr;
+  const float *Ap = nullptr, *b = nullptr;
+  float bscale = 1.0f;       // the right-hand side is bscale * b (the Hessian-free solver's -g)
+  double *pap = nullptr;     // [cg_nwg(n)] partials of p.Ap
+  double *rr = nullptr;      // [2][cg_nwg(n)] partials of r.r: iteration k reads table k & 1, writes (k + 1) & 1
+  double *xd = nullptr;      // [3][cg_nwg(n)] partials of x.b, x.r, x.x (cg_xdots)
+  double *st = nullptr;      // CG_N status words
+  int *abort = nullptr;      // the solver's abort word
+  int max_iters = 0;
+  double tol2 = 0.0;         // rtol^2
+};
+// x = 0, r = p = bscale b, table 0 of r.r; then one workgroup: rr0, and a zero or non-finite rr0 stops at once
+void cg_init(hipStream_t s, const CgArgs &a);
+void cg_pap(hipStream_t s, const CgArgs &a);
+void cg_step(hipStream_t s, const CgArgs &a, int k);
+void cg_dir(hipStream_t s, const CgArgs &a, int k);
+// after the solve: x.(bscale b), x.r, x.x into the status block (two launches, no abort word)
+void cg_xdots(hipStream_t s, const CgArgs &a);
 
 // BASELINE config 5's synthetic regression data on the device (synth.hip).
 void synth_regression(hipStream_t s, long long row0, long long N, int In, unsigned seed_x, unsigned seed_t, float *X,
@@ -321,7 +356,8 @@ void epoch_loss_acc(hipStream_t s, const double *scal, long long rows, float *es
 // u = (sum_i W[slot_i]) / cnt  in logical order, fp64 accumulation
 void average_slots(hipStream_t s, long long n, const float *W, long long ld, const int *h_slots, int cnt, float *u);
 // out = a + c*b
-void lincomb(hipStream_t s, long long n, const float *a, double c, const float *b, float *out);
+void lincomb(hipStream_t s, long long n, const float *a, double c, const float *b, float *out,
+             const int *abort = nullptr);
 // G[r * ld + e] += lambda w[e], r < rows, e < n (finalize_kernel's fp32 update on a block of gradients)
 void add_l2_rows(hipStream_t s, long long n, int rows, long long ld, float *G, const float *w, double lambda);
 void gather_rows(hipStream_t s, const float *src, long long ld, const int *idx, long long count, int cols,

@@ -1214,17 +1214,28 @@ void Mlp::hvp(const float *P, const float *V, const float *X, const float *Y, co
 void Mlp::gnvp(const float *P, const float *V, const float *X, const float *Y, const int *idx, long long B,
                double inv_scale, double lambda, float *Gv) {
   LBF_REQUIRE(P && V && Gv && B >= 0 && (B == 0 || (X && Y)), "gnvp: bad argument");
+  gn_prepare(P, X, Y, idx, B);
+  gn_apply(P, V, X, Y, idx, B, inv_scale, lambda, Gv);
+}
+
+void Mlp::gn_prepare(const float *P, const float *X, const float *, const int *idx, long long B) {
+  if (B == 0) return; // an empty share has no activations
+  ensure(B);
+  rpass_ensure(B);
+  forward(P, X, idx, B, int(layers_.size()));
+}
+
+void Mlp::gn_apply(const float *P, const float *V, const float *X, const float *Y, const int *idx, long long B,
+                   double inv_scale, double lambda, float *Gv) {
   hipStream_t s = ctx_->stream;
   const int nl = int(layers_.size());
+  const int *ab = ctx_->abort;
   if (B == 0) { // a data-parallel rank with an empty share still joins the all-reduce
     LBF_HIP(hipMemsetAsync(Gv, 0, nparams_ * sizeof(float), s));
     if (ctx_->dp()) ctx_->allreduce(Gv, nparams_);
-    if (lambda != 0.0) lincomb(s, (long long)nparams_, Gv, lambda, V, Gv);
+    if (lambda != 0.0) lincomb(s, (long long)nparams_, Gv, lambda, V, Gv, ab);
     return;
   }
-  ensure(B);
-  rpass_ensure(B);
-  forward(P, X, idx, B, nl);
   // ---- R-forward: T0 = A_{l-1} V_l + v_l in RZ_[l], T1 = R{A_{l-1}} W_l in T1_; only R{A_l} is kept ----
   const Layer &Lo = layers_[size_t(nl - 1)];
   for (int l = 0; l < nl; ++l) {
@@ -1240,11 +1251,11 @@ void Mlp::gnvp(const float *P, const float *V, const float *X, const float *Y, c
     // ---- the loss's Hessian on R{Z_L}: the output delta M_L of the backward pass ----
     if (l == nl - 1) {
       if (loss_ == LOSS_XENT)
-        gn_out_xent(s, B, Lo.out, A_[size_t(l)].get(), Y, idx, t0, t1, inv_scale, RD_[size_t(l)].get());
+        gn_out_xent(s, B, Lo.out, A_[size_t(l)].get(), Y, idx, t0, t1, inv_scale, RD_[size_t(l)].get(), ab);
       else
-        gn_out_mse(s, B * Lo.out, A_[size_t(l)].get(), t0, t1, Lo.act, inv_scale, RD_[size_t(l)].get());
+        gn_out_mse(s, B * Lo.out, A_[size_t(l)].get(), t0, t1, Lo.act, inv_scale, RD_[size_t(l)].get(), ab);
     } else {
-      gn_act(s, B * L.out, A_[size_t(l)].get(), t0, t1, L.act, RA_[size_t(l)].get());
+      gn_act(s, B * L.out, A_[size_t(l)].get(), t0, t1, L.act, RA_[size_t(l)].get(), ab);
     }
   }
   // ---- backward: (G v)_l = [A_{l-1} | 1]^T M_l, M_{l-1} = (M_l W_l^T) .* act'(A_{l-1}) ----
@@ -1254,7 +1265,86 @@ void Mlp::gnvp(const float *P, const float *V, const float *X, const float *Y, c
     if (l > 0) rpass_back_prod(B, l, RD_[size_t(l)].get(), P, layers_[size_t(l - 1)].act, RD_[size_t(l - 1)].get());
   }
   if (ctx_->dp()) ctx_->allreduce(Gv, nparams_);
-  if (lambda != 0.0) lincomb(s, (long long)nparams_, Gv, lambda, V, Gv);
+  if (lambda != 0.0) lincomb(s, (long long)nparams_, Gv, lambda, V, Gv, ab);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Gauss-Newton conjugate gradients (cg.hip). Every launch of an iteration takes the solver's abort
+// word through ctx_->abort, so the iterations enqueued past the stopping one change nothing: x, r and the status
+// block stay bitwise what the stopping iteration left, whatever `check` is. Under a communicator a frozen
+// iteration still joins its all-reduce; Ap is zeroed in front of every product there, so what the frozen
+// collectives sum in place is zeros (a live product overwrites every element of Ap).
+// ------------------------------------------------------------------------------------------------
+void Mlp::gn_cg(const float *P, const float *b, float bscale, const float *X, const float *Y, const int *idx,
+                long long B, double inv_scale, double damping, int max_iters, double rtol, int check, float *x,
+                CgInfo *info) {
+  LBF_REQUIRE(P && b && x && B >= 0 && (B == 0 || (X && Y)), "gn_cg: bad argument");
+  LBF_REQUIRE(max_iters >= 0 && rtol >= 0.0 && check >= 1, "gn_cg: max_iters >= 0, rtol >= 0, check >= 1");
+  hipStream_t s = ctx_->stream;
+  const long long n = (long long)nparams_;
+  const int nwg = cg_nwg(n);
+  cg_r_.ensure(size_t(n));
+  cg_p_.ensure(size_t(n));
+  cg_ap_.ensure(size_t(n));
+  cg_part_.ensure(size_t(6) * size_t(nwg));
+  cg_st_.ensure(CG_N);
+  cg_abort_.ensure(1);
+  cg_hst_.ensure(CG_N);
+  CgArgs a;
+  a.n = n;
+  a.x = x;
+  a.r = cg_r_.get();
+  a.p = cg_p_.get();
+  a.Ap = cg_ap_.get();
+  a.b = b;
+  a.bscale = bscale;
+  a.pap = cg_part_.get();
+  a.rr = cg_part_.get() + nwg;
+  a.xd = cg_part_.get() + 3 * size_t(nwg);
+  a.st = cg_st_.get();
+  a.abort = cg_abort_.get();
+  a.max_iters = max_iters;
+  a.tol2 = rtol * rtol;
+  struct AbortScope { // ctx->abort points at the solver's word for the duration of the solve
+    Ctx *c;
+    const int *prev;
+    ~AbortScope() { c->abort = prev; }
+  } scope{ctx_, ctx_->abort};
+  LBF_HIP(hipMemsetAsync(cg_abort_.get(), 0, sizeof(int), s));
+  ctx_->abort = cg_abort_.get();
+  gn_prepare(P, X, Y, idx, B);
+  cg_init(s, a);
+  double *hst = cg_hst_.get();
+  auto read_status = [&]() {
+    LBF_HIP(hipMemcpyAsync(hst, cg_st_.get(), CG_N * sizeof(double), hipMemcpyDeviceToHost, s));
+    LBF_HIP(hipStreamSynchronize(s));
+  };
+  int k = 0;
+  for (;;) {
+    const int m = std::min(check, max_iters - k);
+    for (int i = 0; i < m; ++i, ++k) {
+      if (ctx_->dp() && B > 0) zero_fill(s, n, cg_ap_.get());
+      gn_apply(P, a.p, X, Y, idx, B, inv_scale, damping, cg_ap_.get());
+      cg_pap(s, a);
+      cg_step(s, a, k);
+      cg_dir(s, a, k);
+    }
+    read_status();
+    if (int(hst[CG_STATUS]) != CG_RUNNING || k >= max_iters) break;
+  }
+  ctx_->abort = scope.prev;
+  LBF_HIP(hipMemsetAsync(cg_abort_.get(), 0, sizeof(int), s));
+  cg_xdots(s, a);
+  read_status();
+  if (info) {
+    info->iterations = int(hst[CG_ITER]);
+    info->status = int(hst[CG_STATUS]) == CG_RUNNING ? int(CG_MAXITER) : int(hst[CG_STATUS]); // max_iters == 0
+    info->rr0 = hst[CG_RR0];
+    info->rr = hst[CG_RR];
+    info->xb = hst[CG_XB];
+    info->xr = hst[CG_XR];
+    info->xx = hst[CG_XX];
+  }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -185,6 +185,19 @@ public:
   // hvp; it shares hvp's workspace, and the two may be called in any order with any batch sizes.
   void gnvp(const float *P, const float *V, const float *X, const float *Y, const int *idx, long long B,
             double inv_scale, double lambda, float *Gv);
+  // Conjugate gradients on (G(P) + damping I) x = bscale b, G the Gauss-Newton matrix of gnvp on the given batch
+  // (cg.hip), from x = 0. The forward pass runs once (gn_prepare); an iteration is gn_apply on the
+  // direction and three sweeps. The host enqueues `check` iterations, reads the status block and goes on while the
+  // solve is running; the solver's abort word, which ctx->abort points at meanwhile, freezes what was enqueued
+  // past the stopping iteration. x: nparams() floats, any 4-byte aligned pointer. Synchronous.
+  struct CgInfo {
+    int iterations = 0, status = 0; // CG_CONVERGED / CG_MAXITER / CG_BREAKDOWN
+    double rr0 = 0.0, rr = 0.0, xb = 0.0, xr = 0.0, xx = 0.0; // xb = x.(bscale b)
+  };
+  void gn_cg(const float *P, const float *b, float bscale, const float *X, const float *Y, const int *idx,
+             long long B, double inv_scale, double damping, int max_iters, double rtol, int check, float *x,
+             CgInfo *info);
+  const float *cg_residual() const { return cg_r_.get(); } // r of the last gn_cg (null before the first)
   // Device-side evaluation (metrics.hip; replaces the host scan of unified_launcher.hpp:154-199): forward() and
   // the metrics kernel per chunk of chunk_rows rows (0: 65536, or the batch if smaller), so the activation
   // workspace is bounded by the chunk. Every chunk runs the forward plan of the whole batch, so the outputs, and
@@ -260,6 +273,18 @@ private:
   DevBuf<float> T1_, T2_, seg_;
   long long rcap_ = -1;
   void rpass_ensure(long long B); // grows the workspace to B rows
+  // gnvp in two steps. gn_prepare: the workspaces and the unfused forward pass of the batch. gn_apply: the
+  // R-forward, the loss's Hessian, the backward pass, the all-reduce and + lambda V, on the activations
+  // gn_prepare left. The prepared state holds until the next call that writes the activation workspace (forward,
+  // loss_grad, loss_only, evaluate, hvp, gnvp); P, X, Y, idx and B must be gn_prepare's.
+  void gn_prepare(const float *P, const float *X, const float *Y, const int *idx, long long B);
+  void gn_apply(const float *P, const float *V, const float *X, const float *Y, const int *idx, long long B,
+                double inv_scale, double lambda, float *Gv);
+  // gn_cg's state: r, p, Ap, the partial tables [pap | rr x 2 | xdots x 3], the status block, the abort word
+  DevBuf<float> cg_r_, cg_p_, cg_ap_;
+  DevBuf<double> cg_part_, cg_st_;
+  DevBuf<int> cg_abort_;
+  PinnedBuf<double> cg_hst_;
   // the R-pass products of layer l on B rows, with the forward, dW and dX plans of ensure(B)
   void rpass_linear_fwd(long long B, int l, const float *Wsrc, const float *in, const int *rows, bool with_bias,
                         float *out);

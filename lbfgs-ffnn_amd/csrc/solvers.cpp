@@ -1413,4 +1413,113 @@ int run_sgd(Mlp *net, const lbf_sgd_params &prm, float *d_params, const float *X
   return done;
 }
 
+// ================================================================================================
+// Hessian-free: truncated Newton with the Gauss-Newton matrix (Martens 2010). The step solves
+// (G + (l2 + lambda) I) p = -g by device-side CG (Mlp::gn_cg, one forward pass per solve); the host sees one
+// status block per `cg_check` CG iterations and one loss per line-search trial. Every decision is taken on the
+// host from fp64 words that are all-reduced (or replicated) under a communicator, so the ranks agree.
+// ================================================================================================
+int run_hf(Mlp *net, const lbf_hf_params &prm, float *d_params, const float *X, const float *Y, long long n_local,
+           long long n_global, lbf_record *rec, lbf_solve_info *info) {
+  LBF_REQUIRE(d_params && n_local >= 0 && n_global > 0 && (n_local == 0 || (X && Y)), "bad argument");
+  LBF_REQUIRE(prm.max_iters >= 0 && prm.cg_iters >= 0 && prm.cg_rtol >= 0.0 && prm.cg_check >= 1 &&
+                  prm.max_line_iters >= 1 && prm.damping0 >= 0.0 && prm.rho > 0.0 && prm.rho < 1.0,
+              "hf: bad parameter");
+  Ctx *c = net->ctx();
+  LBF_REQUIRE(prm.curv_rows >= 0 && prm.curv_rows <= n_local, "hf: curv_rows must lie in [0, n_local]");
+  LBF_REQUIRE(prm.curv_rows == 0 || !c->comm, "hf: curv_rows > 0 runs on one rank (the window has no shard split)");
+  c->set_device();
+  hipStream_t s = c->stream;
+  const long long n = (long long)net->nparams();
+  const int In = net->layers().front().in, Out = net->layers().back().out;
+  const int nww = ww_partials_n(n);
+  DevBuf<float> g(size_t(round4(n + 2))), p(size_t(std::max(1LL, n))), trial(size_t(std::max(1LL, n)));
+  DevBuf<double> scal(SC_N), wwp{size_t(nww)};
+  PinnedBuf<double> hs;
+  hs.ensure(SC_N);
+  const long long evals0 = net->evals(), rows0 = net->rows(), lo0 = net->loss_only_evals();
+  const double l2 = net->l2(), inv = 1.0 / double(n_global);
+  auto read_scal = [&]() {
+    LBF_HIP(hipMemcpyAsync(hs.get(), scal.get(), SC_N * sizeof(double), hipMemcpyDeviceToHost, s));
+    LBF_HIP(hipStreamSynchronize(s));
+  };
+  auto eval = [&]() {
+    net->loss_grad(d_params, g.get(), X, Y, nullptr, n_local, inv, l2, nullptr, scal.get());
+    read_scal();
+  };
+  double lam = prm.damping0;
+  const auto t0 = std::chrono::steady_clock::now();
+  int done = 0, ri = rec ? rec->size : 0;
+  eval();
+  for (int it = 0; it < prm.max_iters; ++it) {
+    const double f = hs[SC_LOSS], gnorm = std::sqrt(hs[SC_TGG]);
+    if (gnorm < prm.tol || !(hs[SC_TGG] > 0.0)) break;
+    // ---- the step: CG on the curvature rows ----
+    const float *Xc = X, *Yc = Y;
+    long long Bc = n_local;
+    double cinv = inv;
+    if (prm.curv_rows > 0) {
+      const long long off = ((long long)it * prm.curv_rows) % (n_local - prm.curv_rows + 1);
+      Xc = X + off * In;
+      Yc = Y + off * Out;
+      Bc = prm.curv_rows;
+      cinv = 1.0 / double(prm.curv_rows);
+    }
+    Mlp::CgInfo ci;
+    net->gn_cg(d_params, g.get(), -1.0f, Xc, Yc, nullptr, Bc, cinv, l2 + lam, prm.cg_iters, prm.cg_rtol, prm.cg_check,
+               p.get(), &ci);
+    const double q = -0.5 * (ci.xb + ci.xr) - 0.5 * lam * ci.xx; // g.p + 0.5 p^T (G + l2 I) p
+    const double gp = -ci.xb;
+    // ---- backtracking on the full objective ----
+    double alpha = 1.0, f1 = f;
+    int trials = 0, accepted = 0;
+    for (int t = 0; t < prm.max_line_iters; ++t) {
+      axpy_to(s, n, d_params, float(alpha), p.get(), trial.get(), wwp.get());
+      net->loss_only(trial.get(), X, Y, nullptr, n_local, inv, scal.get(), l2, WwPart{wwp.get(), nww});
+      read_scal();
+      const double ft = hs[SC_LOSS];
+      if (t == 0) f1 = ft;
+      ++trials;
+      if (ft <= f + prm.c1 * alpha * gp) {
+        accepted = 1;
+        break;
+      }
+      alpha *= prm.rho;
+    }
+    if (accepted) LBF_HIP(hipMemcpyAsync(d_params, trial.get(), size_t(n) * sizeof(float), hipMemcpyDeviceToDevice, s));
+    // ---- Levenberg-Marquardt damping from the first trial's reduction ratio ----
+    const double ratio = q < 0.0 ? (f1 - f) / q : 0.0; // no model decrease (a CG breakdown at x = 0): damp more
+    if (ratio < prm.ratio_lo) lam *= prm.damp_up;
+    else if (ratio > prm.ratio_hi) lam *= prm.damp_down;
+    if (it < prm.trace_cap) {
+      if (prm.damping_trace) prm.damping_trace[it] = lam;
+      if (prm.ratio_trace) prm.ratio_trace[it] = ratio;
+      if (prm.cg_trace) prm.cg_trace[it] = ci.iterations;
+    }
+    if (rec && ri < rec->cap) {
+      const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      if (rec->loss) rec->loss[ri] = f;
+      if (rec->grad_norm) rec->grad_norm[ri] = gnorm;
+      if (rec->time_ms) rec->time_ms[ri] = ms;
+      if (rec->alpha) rec->alpha[ri] = accepted ? alpha : 0.0;
+      if (rec->ls_trials) rec->ls_trials[ri] = trials;
+      if (rec->accepted) rec->accepted[ri] = accepted;
+      rec->size = std::max(rec->size, ri + 1);
+      ++ri;
+    }
+    ++done;
+    eval(); // the next iteration's f and g; after the last one, the final point's
+  }
+  if (info) {
+    std::memset(info, 0, sizeof(*info));
+    info->iterations = done;
+    info->n_evals = net->evals() - evals0;
+    info->n_rows = net->rows() - rows0;
+    info->n_loss_only = net->loss_only_evals() - lo0;
+    info->final_loss = hs[SC_LOSS];
+    info->final_grad_norm = std::sqrt(hs[SC_TGG]);
+  }
+  return done;
+}
+
 } // namespace lbf

@@ -342,6 +342,11 @@ int run_gd(Mlp *net, const lbf_gd_params &prm, float *d_params, const float *X, 
 int run_sgd(Mlp *net, const lbf_sgd_params &prm, float *d_params, const float *X, const float *Y, long long N,
             lbf_record *rec, lbf_solve_info *info);
 
+// Hessian-free solver (lbfgs_amd.h lbf_hf_solve): Gauss-Newton CG steps with Levenberg-Marquardt
+// damping and a backtracking line search; returns the outer iterations done.
+int run_hf(Mlp *net, const lbf_hf_params &prm, float *d_params, const float *X, const float *Y, long long n_local,
+           long long n_global, lbf_record *rec, lbf_solve_info *info);
+
 // finite_difference_hvp_batch (s_lbfgs.hpp:88-101) up to the last step: wp/wm = u +- eps s, gp/gm = the
 // batch gradients there (1/count scale, + lambda w). y = (gp - gm) / (2 eps) is formed by the caller (the
 // S-LBFGS pair sweep, or diff_scale) in fp32 with the factor rounded once.

@@ -803,12 +803,13 @@ void scal(hipStream_t s, long long n, float alpha, float *x) {
 }
 
 __global__ __launch_bounds__(256) void lincomb_kernel(long long n, const float *a, double c, const float *b,
-                                                      float *out) {
+                                                      float *out, const int *abort) {
+  if (abort && *abort) return;
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < n) out[e] = float(double(a[e]) + c * double(b[e]));
 }
-void lincomb(hipStream_t s, long long n, const float *a, double c, const float *b, float *out) {
-  hipLaunchKernelGGL(lincomb_kernel, dim3(unsigned(cdiv(n, 256))), dim3(256), 0, s, n, a, c, b, out);
+void lincomb(hipStream_t s, long long n, const float *a, double c, const float *b, float *out, const int *abort) {
+  hipLaunchKernelGGL(lincomb_kernel, dim3(unsigned(cdiv(n, 256))), dim3(256), 0, s, n, a, c, b, out, abort);
   LBF_KERNEL_CHECK();
 }
 

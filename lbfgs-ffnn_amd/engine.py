@@ -15,8 +15,10 @@ import numpy as np
 import torch
 
 from ._lib import (ACTS, HVP_MODES, INIT_CPU, INIT_CUDA, LOSSES, check_l2, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED, SLBFGS_DP_SLICED,
-                   EvalResultC, GdParams, LbfError, LbfgsParams, Record, SgdParams, SlbfgsParams, SolveInfo, check, lib,
+                   CgInfo, CgParams, EvalResultC, GdParams, HfParams, LbfError, LbfgsParams, Record, SgdParams, SlbfgsParams, SolveInfo, check, lib,
                    ptr)
+
+_check_rc = check  # for Mlp.gn_cg, whose `check` argument is the CG status-read interval
 
 
 class Context:
@@ -342,6 +344,38 @@ class Mlp:
                                  B, inv_scale, l2, ptr(out, numel=n)), "lbf_mlp_gnvp")
         return out
 
+    def gn_cg(self, params: torch.Tensor, b: torch.Tensor, X: torch.Tensor, Y: torch.Tensor,
+              idx: Optional[torch.Tensor] = None, inv_scale: Optional[float] = None, l2: float = 0.0,
+              damping: Optional[float] = None, max_iters: Optional[int] = None, rtol: Optional[float] = None,
+              check: Optional[int] = None, out: Optional[torch.Tensor] = None, residual: bool = False):
+        """Conjugate gradients on (G(params) + damping I) x = b from x = 0 (lbf_mlp_gn_cg), G as in gnvp on the same
+        batch; `l2` is another name for the damping (the two add). One forward pass for the whole solve, every CG
+        scalar on the device; `check` iterations are enqueued between two status reads and the result does not
+        depend on it. Returns (x, info): info has iterations, status (0 converged to rtol, 1 max_iters, 2 p.Ap <= 0),
+        rr0, rr, xb, xr, xx and, with residual=True, "r": the recurrence residual as a tensor."""
+        B = int(idx.numel()) if idx is not None else int(X.shape[0])
+        if inv_scale is None:
+            inv_scale = 1.0 / max(B, 1)
+        out = self.new_params() if out is None else out
+        self._check_data(X, Y)
+        n = self.nparams
+        p = CgParams()
+        lib().lbf_cg_default_params(C.byref(p))
+        p.damping = float(l2) + (0.0 if damping is None else float(damping))
+        for k, v in (("max_iters", max_iters), ("rtol", rtol), ("check", check)):
+            if v is not None:
+                setattr(p, k, v)
+        ci = CgInfo()
+        _check_rc(lib().lbf_mlp_gn_cg(self.h, ptr(params, numel=n), ptr(b, numel=n), ptr(X), ptr(Y),
+                                      ptr(idx, torch.int32), B, inv_scale, C.byref(p), ptr(out, numel=n),
+                                      C.byref(ci)), "lbf_mlp_gn_cg")
+        info = {k: getattr(ci, k) for k, _ in CgInfo._fields_}
+        if residual:
+            r = torch.empty(n, dtype=torch.float32, device=out.device)
+            _check_rc(lib().lbf_mlp_gn_cg_residual(self.h, ptr(r, numel=n)), "lbf_mlp_gn_cg_residual")
+            info["r"] = r
+        return out, info
+
     def fd_hvp(self, params: torch.Tensor, v: torch.Tensor, X: torch.Tensor, Y: torch.Tensor,
                idx: Optional[torch.Tensor] = None, inv_scale: Optional[float] = None, l2: float = 0.0,
                eps: float = 1e-4, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -596,6 +630,42 @@ def gd_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, n
     check(lib().lbf_gd_solve(net.h, C.byref(p), ptr(params), ptr(X), ptr(Y), n_local, int(n_global or n_local),
                              C.byref(hist.rec), C.byref(info)), "lbf_gd_solve")
     return hist.as_dict(), info
+
+
+def hf_params(**kw) -> HfParams:
+    """lbf_hf_params with the library's defaults and the given fields (max_iters, tol, cg_iters, cg_rtol, cg_check,
+    damping0, damp_up, damp_down, ratio_lo, ratio_hi, c1, rho, max_line_iters, curv_rows); the trace pointers are
+    hf_solve's. An unknown keyword raises LbfError."""
+    p = HfParams()
+    lib().lbf_hf_default_params(C.byref(p))
+    settable = {k for k, _ in HfParams._fields_} - {"damping_trace", "ratio_trace", "cg_trace", "trace_cap"}
+    for k, v in kw.items():
+        if k not in settable:
+            raise LbfError(f"hf_params: unknown parameter {k!r} (known: {', '.join(sorted(settable))})")
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def hf_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, n_global: Optional[int] = None,
+             **kw):
+    """Hessian-free solver (lbf_hf_solve): Gauss-Newton CG steps with Levenberg-Marquardt damping and a
+    backtracking line search on the network's loss + its l2; params updated in place. kw: see hf_params.
+    Returns (hist, info, traces): traces = {"damping", "ratio", "cg"}, one entry per outer iteration."""
+    p = hf_params(**kw)
+    cap = max(int(p.max_iters), 1)
+    damping, ratio, cg = np.full(cap, np.nan), np.full(cap, np.nan), np.zeros(cap, np.int32)
+    p.damping_trace = damping.ctypes.data_as(C.POINTER(C.c_double))
+    p.ratio_trace = ratio.ctypes.data_as(C.POINTER(C.c_double))
+    p.cg_trace = cg.ctypes.data_as(C.POINTER(C.c_int))
+    p.trace_cap = cap
+    hist = History(cap)
+    info = SolveInfo()
+    n_local = int(X.shape[0])
+    check(lib().lbf_hf_solve(net.h, C.byref(p), ptr(params), ptr(X), ptr(Y), n_local, int(n_global or n_local),
+                             C.byref(hist.rec), C.byref(info)), "lbf_hf_solve")
+    k = int(info.iterations)
+    return hist.as_dict(), info, {"damping": damping[:k], "ratio": ratio[:k], "cg": cg[:k]}
 
 
 def sgd_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, record: bool = True, **kw):

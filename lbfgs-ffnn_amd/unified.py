@@ -52,6 +52,12 @@ class UnifiedConfig:
                                  # applies a non-zero value like UnifiedLauncher.setL2, and it then stays)
     curvature: str = "fd"        # UnifiedSLBFGS's curvature pairs (HIP extension): "fd" (the reference's finite
                                  # difference), "exact" (R-operator H s) or "gauss_newton" (G s, always y.s > 0)
+    # UnifiedHF (HIP extension): CG iterations and relative residual per step, the initial damping, and the rows of
+    # the curvature window (0: all local rows; > 0 is single rank, like UnifiedSGD)
+    cg_iters: int = 50
+    cg_rtol: float = 0.1
+    damping: float = 1.0
+    curv_rows: int = 0
     # Validation-monitored training (HIP extension; UnifiedLBFGS and UnifiedSLBFGS). eval_every > 0: the test split
     # is evaluated on the device at iteration 0, every eval_every iterations (epochs for S-LBFGS) and at the end.
     eval_every: int = 0          # 0: off (the unmonitored code path)
@@ -334,6 +340,27 @@ class UnifiedGD(UnifiedOptimizer):
             rec.record(i, float(hist["loss"][i]), float(hist["grad_norm"][i]), float(hist["time_ms"][i]))
         self.info = info
         self.history = hist
+        return rec
+
+
+class UnifiedHF(UnifiedOptimizer):
+    """Hessian-free (truncated Newton) training (HIP extension, no reference counterpart): engine.hf_solve with the
+    config's max_iters, tolerance, cg_iters, cg_rtol, damping (the initial one) and curv_rows; the loss and l2 are
+    the network's. The damping, reduction-ratio and CG-iteration traces are kept in self.traces."""
+
+    def optimize(self, net, data, config):
+        if config.eval_every > 0:
+            raise LbfError("UnifiedHF has no resumable form: eval_every > 0 needs UnifiedLBFGS or UnifiedSLBFGS")
+        hist, info, traces = engine.hf_solve(net.mlp, net.params, data.x, data.y, n_global=data.n_global,
+                                             max_iters=config.max_iters, tol=config.tolerance,
+                                             cg_iters=config.cg_iters, cg_rtol=config.cg_rtol,
+                                             damping0=config.damping, curv_rows=config.curv_rows)
+        rec = IterationRecorder()
+        for i in range(len(hist["loss"])):
+            rec.record(i, float(hist["loss"][i]), float(hist["grad_norm"][i]), float(hist["time_ms"][i]))
+        self.info = info
+        self.history = hist
+        self.traces = traces
         return rec
 
 
