@@ -414,6 +414,60 @@ void lbf_hf_default_params(lbf_hf_params *p);
 int lbf_hf_solve(lbf_mlp *net, const lbf_hf_params *prm, float *d_params, const float *d_X, const float *d_Y,
                  long long n_local, long long n_global, lbf_record *rec, lbf_solve_info *info);
 
+/* ---- OWL-QN: L1-regularised L-BFGS (extension; Andrew & Gao 2007, libLBFGS's orthantwise_c). New functions and
+ * structs only: LBF_ABI_VERSION stays 3.
+ *
+ * Minimises F(w) = f(w) + sum_i c_i |w_i| with f the objective of lbf_gd_solve (the network's loss, a mean over
+ * n_global, + 0.5 l2 |w|^2 with the network's l2; n_local rows on this rank). c_i = l1 on every weight; on the
+ * biases c_i = 0, or l1 when l1_bias != 0. Iteration k from (x, f, g):
+ *   1. pseudo-gradient pg_i = g_i + c_i (x_i > 0), g_i - c_i (x_i < 0); at x_i == 0: g_i - c_i if that is > 0,
+ *      else g_i + c_i if that is < 0, else +0 (each one fp32 add with c_i = (float)l1). Stop when ||pg|| < tol;
+ *   2. d = -H pg by the two-loop recursion over the stored pairs (gamma = s.y / y.y of the newest, d = -pg without
+ *      pairs); then d_i = 0 wherever d_i pg_i >= 0 (tested on the signs);
+ *   3. orthant xi_i = sign(x_i), or sign(-pg_i) where x_i == 0 (xi_i = 0: the coordinate stays zero);
+ *   4. backtracking from alpha = 1 (min(1, 1/||pg||) at k = 0), alpha *= rho after a failure, at most
+ *      max_line_iters trials. Trial point: t = fmaf(alpha, d_i, x_i), x+_i = t where t != 0 has the sign xi_i, else
+ *      +0. Accepted when F(x+) <= F(x) + c1 sum_i pg_i (x+_i - x_i), F(x+) from a loss-only evaluation. If every
+ *      trial fails the point stays, the row records accepted = 0 and alpha = 0, and the solve ends there: a further
+ *      iteration would repeat this one;
+ *   5. on acceptance the gradient g+ comes from the backward pass of the accepted trial's forward state;
+ *      s = x+ - x, y = g+ - g (the smooth gradients, never pg) enter the ring of m pairs when y.s > 1e-10;
+ *   6. lbf_record row: F and ||pg|| at the iteration's start point, alpha, ls_trials, accepted.
+ * The sign test of step 2 and the projection of steps 3 and 4 apply to the penalised coordinates: every weight,
+ * whatever l1 is, and the biases when l1_bias != 0. Such a coordinate changes sign only through an iteration at
+ * zero. So l1 = 0 is legal but still orthant-wise; it is not lbf_lbfgs_solve. The other coordinates (the biases
+ * when l1_bias == 0) are free: pg_i = g_i, x+_i = fmaf(alpha, d_i, x_i), and no step sets them to zero.
+ * info: final_loss = F and final_grad_norm = ||pg|| at the end; n_evals the gradient evaluations (the start point
+ * and the accepted trials), n_loss_only the trials, n_grad_after_loss the accepted ones. stats (nullable): of the
+ * final point, over the penalised coordinates. zeros_trace (nullable, trace_cap entries): the penalised coordinates
+ * that are exactly zero after each iteration. With a communicator every rank evaluates its rows, and runs the same
+ * vector arithmetic on the all-reduced loss and gradient: identical decisions, no further collective.
+ * LBF_ERR_INVALID: null handles, l1 < 0 or non-finite, m outside 0..128, max_iters < 0, rho outside (0, 1),
+ * max_line_iters < 1. */
+typedef struct lbf_owlqn_params {
+  int m, max_iters; double tol;            /* 10, 100, 1e-6 */
+  double l1; int l1_bias;                  /* 0, 0 */
+  double c1, rho; int max_line_iters;      /* 1e-4, 0.5, 20 */
+  long long *zeros_trace; int trace_cap;   /* nullable: zero weights after each iteration */
+} lbf_owlqn_params;
+typedef struct lbf_owlqn_stats { long long zeros, penalised; double l1_term, pg_norm; } lbf_owlqn_stats;
+void lbf_owlqn_default_params(lbf_owlqn_params *p);
+int  lbf_owlqn_solve(lbf_mlp *net, const lbf_owlqn_params *prm, float *d_params, const float *d_X,
+                     const float *d_Y, long long n_local, long long n_global, lbf_record *rec,
+                     lbf_solve_info *info, lbf_owlqn_stats *stats /* nullable */);
+/* The two sweeps on their own, for callers with their own objective: each is one launch over the parameters and a
+ * one-workgroup finisher, every sum an fp64 sum in a fixed order (bitwise reproducible). All vectors hold the
+ * network's parameter count, 4-byte aligned, and must not overlap.
+ * lbf_mlp_l1_pseudo_grad: d_pg = step 1's pseudo-gradient at d_x with smooth gradient d_g; h_stats (nullable):
+ *   zeros, penalised, l1_term = l1 sum |x_i| over the penalised, pg_norm.
+ * lbf_mlp_l1_trial: d_xnew = step 4's trial point from the raw direction d_d (step 2's sign test is applied
+ *   inside); h_l1_term, h_ww = xnew.xnew, h_dec = pg.(xnew - x), h_zeros (each nullable). */
+int  lbf_mlp_l1_pseudo_grad(lbf_mlp *net, const float *d_x, const float *d_g, double l1, int l1_bias,
+                            float *d_pg, lbf_owlqn_stats *h_stats);
+int  lbf_mlp_l1_trial(lbf_mlp *net, const float *d_x, const float *d_d, const float *d_pg, double l1,
+                      int l1_bias, float alpha, float *d_xnew, double *h_l1_term, double *h_ww,
+                      double *h_dec /* pg.(xnew - x) */, long long *h_zeros);
+
 int lbf_slbfgs_solve(lbf_mlp *net, const lbf_slbfgs_params *prm, float *d_params, const float *d_X,
                      const float *d_Y, long long N, lbf_record *rec, lbf_solve_info *info);
 /* Stateful S-LBFGS (benchmarking, and callers that check progress between epochs): begin copies nothing

@@ -405,6 +405,58 @@ private:
   long long curv_rows_ = 0;
 };
 
+/// OWL-QN minimizer on a HipNetwork (HIP extension, no reference counterpart: lbf_owlqn_solve, L-BFGS on the
+/// network's loss + its l2 + l1 |w|_1 with the orthant-wise pseudo-gradient, direction and projection). Like HipHF,
+/// solve() minimises the network's own objective on input / target and does not call loss_grad; n must be the
+/// network's parameter count.
+class HipOWLQN : public HipMinimizerBase {
+public:
+  HipOWLQN(HipHandle &handle, HipNetwork &net) : HipMinimizerBase(handle), net_(net) {}
+  void setL1(double l1, bool on_biases = false) {
+    l1_ = l1;
+    l1_bias_ = on_biases ? 1 : 0;
+  }
+  void setHistorySize(int m) { m_ = m; }
+  /// of the last solve's final point: zero and penalised coordinates, l1 |w|_1, the pseudo-gradient norm
+  const lbf_owlqn_stats &stats() const { return stats_; }
+
+  void solve(int n, HipScalar *params, const HipScalar *input, const HipScalar *target, int batch,
+             const LossGradFun &) override {
+    if (n <= 0 || params == nullptr) {
+      last_iterations_ = 0;
+      return;
+    }
+    lbf_owlqn_params prm;
+    lbf_owlqn_default_params(&prm);
+    prm.m = m_;
+    prm.max_iters = max_iters_;
+    prm.tol = tol_;
+    prm.l1 = l1_;
+    prm.l1_bias = l1_bias_;
+    prm.max_line_iters = max_line_iters_;
+    prm.c1 = c1_;
+    prm.rho = rho_;
+    lbf_record rec{};
+    lbf_record *rp = nullptr;
+    if (recorder_) {
+      recorder_->reset();
+      rec = recorder_->view();
+      rp = &rec;
+    }
+    lbf_solve_info info{};
+    hip_check(lbf_owlqn_solve(net_.raw(), &prm, params, input, target, batch, batch, rp, &info, &stats_),
+              "lbf_owlqn_solve");
+    if (recorder_) recorder_->set_size(rec.size);
+    last_iterations_ = info.iterations;
+  }
+
+private:
+  HipNetwork &net_;
+  double l1_ = 0.0;
+  int l1_bias_ = 0, m_ = 10;
+  lbf_owlqn_stats stats_{};
+};
+
 /// Column-major host matrix with the subset of Eigen::MatrixXd's interface the launcher uses.
 class HostMatrix {
 public:
@@ -474,6 +526,7 @@ struct UnifiedConfig {
   int cg_iters = 50;
   double cg_rtol = 0.1;
   double damping = 1.0;
+  double l1 = 0.0; ///< HIP extension: UnifiedOWLQN_HIP's L1 penalty on the weights; the other optimisers do not read it
 };
 /// src/unified_optimization.hpp:54-59 (HostMatrix instead of Eigen::MatrixXd)
 struct UnifiedDataset {
@@ -637,6 +690,35 @@ public:
     hip_mlp::hip_check(lbf_hf_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n_train, n_train, &rec,
                                     &info),
                        "lbf_hf_solve");
+    recorder.set_size(rec.size);
+    write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
+  }
+};
+
+/// L1-regularised L-BFGS (HIP extension, no reference counterpart): lbf_owlqn_solve with the config's m_param,
+/// max_iters and tolerance and, where the config is this header's own, its l1.
+class UnifiedOWLQN_HIP : public UnifiedOptimizer<HipBackend> {
+public:
+  lbf_owlqn_stats stats{};
+  void optimize(hip_mlp::HipHandle &, NetworkWrapper<HipBackend> &net, const UnifiedDataset &host_data,
+                hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dx, hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dy,
+                const UnifiedConfig &c) override {
+    const long n_train = long(host_data.train_x.cols());
+    auto &nw = net.getInternal();
+    lbf_owlqn_params prm;
+    lbf_owlqn_default_params(&prm);
+    prm.m = c.m_param;
+    prm.max_iters = c.max_iters;
+    prm.tol = c.tolerance;
+#ifndef LBF_USE_REFERENCE_UNIFIED_TYPES // the reference's own UnifiedConfig has no such member
+    prm.l1 = c.l1;
+#endif
+    recorder.init(c.max_iters);
+    lbf_record rec = recorder.view();
+    lbf_solve_info info{};
+    hip_mlp::hip_check(lbf_owlqn_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n_train, n_train,
+                                       &rec, &info, &stats),
+                       "lbf_owlqn_solve");
     recorder.set_size(rec.size);
     write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
   }

@@ -66,6 +66,17 @@ class HfParams(C.Structure):  # lbf_hf_params
                 ("ratio_trace", C.POINTER(C.c_double)), ("cg_trace", C.POINTER(C.c_int)), ("trace_cap", C.c_int)]
 
 
+class OwlqnParams(C.Structure):  # lbf_owlqn_params
+    _fields_ = [("m", C.c_int), ("max_iters", C.c_int), ("tol", C.c_double), ("l1", C.c_double),
+                ("l1_bias", C.c_int), ("c1", C.c_double), ("rho", C.c_double), ("max_line_iters", C.c_int),
+                ("zeros_trace", C.POINTER(C.c_longlong)), ("trace_cap", C.c_int)]
+
+
+class OwlqnStats(C.Structure):  # lbf_owlqn_stats
+    _fields_ = [("zeros", C.c_longlong), ("penalised", C.c_longlong), ("l1_term", C.c_double),
+                ("pg_norm", C.c_double)]
+
+
 class Record(C.Structure):
     _fields_ = [("loss", C.POINTER(C.c_double)), ("grad_norm", C.POINTER(C.c_double)),
                 ("time_ms", C.POINTER(C.c_double)), ("alpha", C.POINTER(C.c_double)),
@@ -176,6 +187,12 @@ def lib():
         "lbf_hf_default_params": (None, [C.POINTER(HfParams)]),
         "lbf_hf_solve": (C.c_int, [_vp, C.POINTER(HfParams), _vp, _vp, _vp, C.c_longlong, C.c_longlong,
                                    C.POINTER(Record), C.POINTER(SolveInfo)]),
+        "lbf_owlqn_default_params": (None, [C.POINTER(OwlqnParams)]),
+        "lbf_owlqn_solve": (C.c_int, [_vp, C.POINTER(OwlqnParams), _vp, _vp, _vp, C.c_longlong, C.c_longlong,
+                                      C.POINTER(Record), C.POINTER(SolveInfo), C.POINTER(OwlqnStats)]),
+        "lbf_mlp_l1_pseudo_grad": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_int, _vp, C.POINTER(OwlqnStats)]),
+        "lbf_mlp_l1_trial": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_int, C.c_float, _vp, _dp, _dp, _dp,
+                                       C.POINTER(C.c_longlong)]),
         "lbf_mlp_evaluate": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_int, C.c_longlong,
                                        C.POINTER(EvalResultC), _vp, _vp, _vp]),
     }
@@ -197,7 +214,8 @@ EXPORTS = ("lbf_last_error lbf_version lbf_abi_version lbf_ctx_create lbf_ctx_de
            "lbf_sample_indices lbf_synth_regression lbf_gd_default_params lbf_sgd_default_params lbf_gd_solve "
            "lbf_sgd_solve lbf_idx_read_images lbf_idx_read_labels lbf_mlp_hvp lbf_mlp_fd_hvp lbf_mlp_loss "
            "lbf_mlp_set_loss lbf_mlp_get_loss lbf_mlp_set_l2 lbf_mlp_get_l2 lbf_mlp_evaluate lbf_mlp_gnvp "
-           "lbf_cg_default_params lbf_mlp_gn_cg lbf_mlp_gn_cg_residual lbf_hf_default_params lbf_hf_solve").split()
+           "lbf_cg_default_params lbf_mlp_gn_cg lbf_mlp_gn_cg_residual lbf_hf_default_params lbf_hf_solve "
+           "lbf_owlqn_default_params lbf_owlqn_solve lbf_mlp_l1_pseudo_grad lbf_mlp_l1_trial").split()
 
 
 def check_l2(l2) -> float:

@@ -583,6 +583,92 @@ int lbf_hf_solve(lbf_mlp *net, const lbf_hf_params *prm, float *d_params, const 
   });
 }
 
+void lbf_owlqn_default_params(lbf_owlqn_params *p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->m = 10;
+  p->max_iters = 100;
+  p->tol = 1e-6;
+  p->c1 = 1e-4;
+  p->rho = 0.5;
+  p->max_line_iters = 20;
+}
+
+int lbf_owlqn_solve(lbf_mlp *net, const lbf_owlqn_params *prm, float *d_params, const float *d_X, const float *d_Y,
+                    long long n_local, long long n_global, lbf_record *rec, lbf_solve_info *info,
+                    lbf_owlqn_stats *stats) {
+  return guard([&] {
+    LBF_REQUIRE(net && prm, "null argument");
+    run_owlqn(net->net.get(), *prm, d_params, d_X, d_Y, n_local, n_global, rec, info, stats);
+  });
+}
+
+namespace {
+// The sweeps' scratch is the context's BLAS-1 scratch: [tables | status block] on the device, the block on the host.
+void owl_sweep_args(lbf_mlp *net, double l1, int l1_bias, OwlArgs &a) {
+  LBF_REQUIRE(std::isfinite(l1) && l1 >= 0.0, "l1 must be finite and >= 0");
+  Ctx &c = net->ctx->c;
+  c.set_device();
+  a.n = (long long)net->net->nparams();
+  a.coef = owl_coef(*net->net, l1, l1_bias);
+  a.l1 = l1;
+  const size_t words = size_t(owl_table_words(a.n));
+  c.part.ensure(words + OWL_N);
+  c.host.ensure(OWL_N);
+  a.tab = c.part.get();
+  a.st = c.part.get() + words;
+}
+void owl_sweep_read(lbf_mlp *net, const OwlArgs &a) {
+  Ctx &c = net->ctx->c;
+  LBF_HIP(hipMemcpyAsync(c.host.get(), a.st, OWL_N * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+  LBF_HIP(hipStreamSynchronize(c.stream));
+}
+} // namespace
+
+int lbf_mlp_l1_pseudo_grad(lbf_mlp *net, const float *d_x, const float *d_g, double l1, int l1_bias, float *d_pg,
+                           lbf_owlqn_stats *h_stats) {
+  return guard([&] {
+    LBF_REQUIRE(net && d_x && d_g && d_pg, "null argument");
+    OwlArgs a;
+    owl_sweep_args(net, l1, l1_bias, a);
+    a.x = d_x;
+    a.g = d_g;
+    a.out = d_pg;
+    owl_pseudo(net->ctx->c.stream, a);
+    owl_pseudo_finish(net->ctx->c.stream, a);
+    owl_sweep_read(net, a);
+    if (h_stats) {
+      const double *h = net->ctx->c.host.get();
+      h_stats->zeros = (long long)h[OWL_ZEROS];
+      h_stats->penalised = owl_penalised_count(*net->net, l1_bias);
+      h_stats->l1_term = h[OWL_L1];
+      h_stats->pg_norm = std::sqrt(h[OWL_PGPG]);
+    }
+  });
+}
+
+int lbf_mlp_l1_trial(lbf_mlp *net, const float *d_x, const float *d_d, const float *d_pg, double l1, int l1_bias,
+                     float alpha, float *d_xnew, double *h_l1_term, double *h_ww, double *h_dec, long long *h_zeros) {
+  return guard([&] {
+    LBF_REQUIRE(net && d_x && d_d && d_pg && d_xnew, "null argument");
+    OwlArgs a;
+    owl_sweep_args(net, l1, l1_bias, a);
+    a.x = d_x;
+    a.d = d_d;
+    a.pg = d_pg;
+    a.alpha = alpha;
+    a.out = d_xnew;
+    owl_trial(net->ctx->c.stream, a);
+    owl_trial_finish(net->ctx->c.stream, a);
+    owl_sweep_read(net, a);
+    const double *h = net->ctx->c.host.get();
+    if (h_l1_term) *h_l1_term = h[OWL_L1];
+    if (h_ww) *h_ww = h[OWL_WW];
+    if (h_dec) *h_dec = h[OWL_DEC];
+    if (h_zeros) *h_zeros = (long long)h[OWL_ZEROS];
+  });
+}
+
 void lbf_slbfgs_default_params(lbf_slbfgs_params *p) {
   if (!p) return;
   p->max_epochs = 1000; // stochastic_minimizer.hpp:44-47

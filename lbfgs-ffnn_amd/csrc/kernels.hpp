@@ -316,6 +316,47 @@ void cg_dir(hipStream_t s, const CgArgs &a, int k);
 // after the solve: x.(bscale b), x.r, x.x into the status block (two launches, no abort word)
 void cg_xdots(hipStream_t s, const CgArgs &a);
 
+// ------------------------------------------------------------------------------------------------
+// Orthant-wise sweeps of OWL-QN (owlqn.hip; the solver is run_owlqn) on F = f + sum_i c_i |x_i|,
+// c_i = float(l1) on the penalised coordinates and 0 on the free ones. Both launch ww_partials_n(n) workgroups over
+// the element blocks of WwPart, write one fp64 partial per workgroup and table, and are followed by a
+// one-workgroup finisher that sums the tables in ww_sum's order into the status block st: no atomics, bitwise
+// reproducible, the grid a function of n only.
+//   owl_pseudo: out = pg, the pseudo-gradient of F at x from the smooth gradient g:
+//                 x > 0: g + c;  x < 0: g - c;  x == 0: g - c if that is > 0, else g + c if that is < 0, else +0.
+//               st: OWL_PGPG = pg.pg, OWL_L1 = l1 sum |x_i| and OWL_ZEROS = the count of x_i == 0, both over the
+//               penalised coordinates.
+//   owl_trial:  out = x+, the trial point of step alpha along the raw two-loop direction d (null: d = -pg):
+//                 penalised i: d_i counts only where d_i and pg_i have opposite signs (the projected direction is
+//                 not stored); t = fmaf(alpha, d_i, x_i); x+_i = t where t != 0 has the sign of x_i (of -pg_i where
+//                 x_i == 0), else +0. Free i: x+_i = fmaf(alpha, d_i, x_i), no test and no projection.
+//               st: OWL_WW = x+.x+, OWL_L1, OWL_ZEROS of x+, OWL_DEC = sum pg_i (x+_i - x_i). The first table of
+//               tab is the WwPart of x+.
+// The sums are fp64 sums of widened fp32 values. All vectors n floats, 4-byte aligned, distinct.
+// ------------------------------------------------------------------------------------------------
+constexpr int OWL_MAXFREE = 16; // one unpenalised range per layer (its biases)
+struct OwlCoef {
+  float c = 0.0f;
+  int nfree = 0; // 0: every coordinate is penalised
+  long long f0[OWL_MAXFREE] = {}, f1[OWL_MAXFREE] = {}; // the free ranges [f0, f1)
+};
+enum { OWL_PGPG = 0, OWL_L1 = 1, OWL_ZEROS = 2, OWL_WW = 3, OWL_DEC = 4, OWL_N = 8 };
+struct OwlArgs {
+  long long n = 0;
+  OwlCoef coef;
+  double l1 = 0.0;     // the penalty is l1 sum |x_i| with l1 as given; the pseudo-gradient adds coef.c = float(l1)
+  const float *x = nullptr, *g = nullptr, *d = nullptr, *pg = nullptr;
+  float alpha = 1.0f;
+  float *out = nullptr;
+  double *tab = nullptr; // owl_table_words(n) words
+  double *st = nullptr;  // OWL_N words
+};
+int owl_table_words(long long n);
+void owl_pseudo(hipStream_t s, const OwlArgs &a); // the sweep: out and the tables
+void owl_trial(hipStream_t s, const OwlArgs &a);
+void owl_pseudo_finish(hipStream_t s, const OwlArgs &a); // the tables of the sweep before it into st
+void owl_trial_finish(hipStream_t s, const OwlArgs &a);
+
 // BASELINE config 5's synthetic regression data on the device (synth.hip).
 void synth_regression(hipStream_t s, long long row0, long long N, int In, unsigned seed_x, unsigned seed_t, float *X,
                       float *Y);

@@ -13,7 +13,8 @@ namespace lbf {
 
 // Per-kernel-class timing with HIP events on the launch stream (enabled by the benchmark only).
 enum ProfKind : int { PK_FWD = 0, PK_DW = 1, PK_DX = 2, PK_LOSS = 3, PK_SLAB = 4, PK_FINAL = 5, PK_GRAM = 6,
-                      PK_COEF = 7, PK_COMBINE = 8, PK_AXPY = 9, PK_ALLREDUCE = 10, PK_METRICS = 11 };
+                      PK_COEF = 7, PK_COMBINE = 8, PK_AXPY = 9, PK_ALLREDUCE = 10, PK_METRICS = 11,
+                      PK_OWL_PSEUDO = 12, PK_OWL_TRIAL = 13 };
 struct ProfRec { int id; size_t a, b; double work; };
 struct Profiler {
   bool on = false;

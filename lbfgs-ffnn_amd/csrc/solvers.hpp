@@ -347,6 +347,15 @@ int run_sgd(Mlp *net, const lbf_sgd_params &prm, float *d_params, const float *X
 int run_hf(Mlp *net, const lbf_hf_params &prm, float *d_params, const float *X, const float *Y, long long n_local,
            long long n_global, lbf_record *rec, lbf_solve_info *info);
 
+// OWL-QN (lbfgs_amd.h lbf_owlqn_solve): L-BFGS on loss + 0.5 l2 |w|^2 + l1 |w|_1 with the pseudo-gradient,
+// the sign-constrained direction and the orthant projection of Andrew & Gao 2007; returns the iterations done.
+int run_owlqn(Mlp *net, const lbf_owlqn_params &prm, float *d_params, const float *X, const float *Y,
+              long long n_local, long long n_global, lbf_record *rec, lbf_solve_info *info, lbf_owlqn_stats *stats);
+// Which coordinates of the network's flat parameters carry the L1 penalty: all of them (l1_bias != 0), or all but
+// each layer's biases. owl_penalised_count: how many that is.
+OwlCoef owl_coef(const Mlp &net, double l1, int l1_bias);
+long long owl_penalised_count(const Mlp &net, int l1_bias);
+
 // finite_difference_hvp_batch (s_lbfgs.hpp:88-101) up to the last step: wp/wm = u +- eps s, gp/gm = the
 // batch gradients there (1/count scale, + lambda w). y = (gp - gm) / (2 eps) is formed by the caller (the
 // S-LBFGS pair sweep, or diff_scale) in fp32 with the factor rounded once.

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from ._lib import (ACTS, HVP_MODES, INIT_CPU, INIT_CUDA, LOSSES, check_l2, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED, SLBFGS_DP_SLICED,
-                   CgInfo, CgParams, EvalResultC, GdParams, HfParams, LbfError, LbfgsParams, Record, SgdParams, SlbfgsParams, SolveInfo, check, lib,
+                   CgInfo, CgParams, EvalResultC, GdParams, HfParams, LbfError, LbfgsParams, OwlqnParams, OwlqnStats, Record, SgdParams, SlbfgsParams, SolveInfo, check, lib,
                    ptr)
 
 _check_rc = check  # for Mlp.gn_cg, whose `check` argument is the CG status-read interval
@@ -89,7 +89,7 @@ class Context:
         return out
 
     PROF_KINDS = ["gemm_fwd", "gemm_dw", "gemm_dx", "loss", "splitk_reduce", "finalize", "gram_sweep",
-                  "hist_coef", "combine_sweep", "ls_axpy", "allreduce", "metrics"]
+                  "hist_coef", "combine_sweep", "ls_axpy", "allreduce", "metrics", "owl_pseudo", "owl_trial"]
 
     def prof_enable(self, on: bool = True):
         check(lib().lbf_prof_enable(self.h, int(on)), "lbf_prof_enable")
@@ -375,6 +375,31 @@ class Mlp:
             _check_rc(lib().lbf_mlp_gn_cg_residual(self.h, ptr(r, numel=n)), "lbf_mlp_gn_cg_residual")
             info["r"] = r
         return out, info
+
+    def l1_pseudo_grad(self, x: torch.Tensor, g: torch.Tensor, l1: float, l1_bias: bool = False,
+                       out: Optional[torch.Tensor] = None):
+        """OWL-QN's pseudo-gradient of f + l1 |w|_1 at x with smooth gradient g (lbf_mlp_l1_pseudo_grad): the
+        penalty is on the weights, and on the biases too with l1_bias. Returns (pg, stats): stats has zeros,
+        penalised, l1_term = l1 sum |x_i| and pg_norm, fp64 sums in a fixed order."""
+        n = self.nparams
+        out = self.new_params() if out is None else out
+        st = OwlqnStats()
+        _check_rc(lib().lbf_mlp_l1_pseudo_grad(self.h, ptr(x, numel=n), ptr(g, numel=n), float(l1), int(bool(l1_bias)),
+                                               ptr(out, numel=n), C.byref(st)), "lbf_mlp_l1_pseudo_grad")
+        return out, {k: getattr(st, k) for k, _ in OwlqnStats._fields_}
+
+    def l1_trial(self, x: torch.Tensor, d: torch.Tensor, pg: torch.Tensor, l1: float, alpha: float = 1.0,
+                 l1_bias: bool = False, out: Optional[torch.Tensor] = None):
+        """OWL-QN's trial point from x along the raw direction d (lbf_mlp_l1_trial): d counts only where it opposes
+        pg, the step fmaf(alpha, d, x) is clipped to +0 where it leaves the orthant of x (of -pg where x is zero).
+        Returns (xnew, sums): sums has l1_term, ww = xnew.xnew, dec = pg.(xnew - x) and zeros."""
+        n = self.nparams
+        out = self.new_params() if out is None else out
+        l1t, ww, dec, zeros = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0), C.c_longlong(0)
+        _check_rc(lib().lbf_mlp_l1_trial(self.h, ptr(x, numel=n), ptr(d, numel=n), ptr(pg, numel=n), float(l1),
+                                         int(bool(l1_bias)), float(alpha), ptr(out, numel=n), C.byref(l1t),
+                                         C.byref(ww), C.byref(dec), C.byref(zeros)), "lbf_mlp_l1_trial")
+        return out, {"l1_term": l1t.value, "ww": ww.value, "dec": dec.value, "zeros": zeros.value}
 
     def fd_hvp(self, params: torch.Tensor, v: torch.Tensor, X: torch.Tensor, Y: torch.Tensor,
                idx: Optional[torch.Tensor] = None, inv_scale: Optional[float] = None, l2: float = 0.0,
@@ -666,6 +691,45 @@ def hf_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, n
                              C.byref(hist.rec), C.byref(info)), "lbf_hf_solve")
     k = int(info.iterations)
     return hist.as_dict(), info, {"damping": damping[:k], "ratio": ratio[:k], "cg": cg[:k]}
+
+
+def owlqn_params(**kw) -> OwlqnParams:
+    """lbf_owlqn_params with the library's defaults and the given fields (m, max_iters, tol, l1, l1_bias, c1, rho,
+    max_line_iters); the trace pointer is owlqn_solve's. An unknown keyword raises LbfError."""
+    p = OwlqnParams()
+    lib().lbf_owlqn_default_params(C.byref(p))
+    settable = {k for k, _ in OwlqnParams._fields_} - {"zeros_trace", "trace_cap"}
+    for k, v in kw.items():
+        if k not in settable:
+            raise LbfError(f"owlqn_params: unknown parameter {k!r} (known: {', '.join(sorted(settable))})")
+        if v is not None:
+            setattr(p, k, int(v) if k == "l1_bias" else v)
+    return p
+
+
+def owlqn_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, n_global: Optional[int] = None,
+                **kw):
+    """OWL-QN (lbf_owlqn_solve): L-BFGS on the network's loss + its l2 + l1 |w|_1 with the orthant-wise
+    pseudo-gradient, direction and projection, so weights become exactly zero; params updated in place. kw: see
+    owlqn_params. l1 = 0 is still orthant-wise (steps are clipped at sign changes), not lbfgs_solve.
+    Returns (hist, info, stats): hist["loss"] is the penalised objective and hist["grad_norm"] the pseudo-gradient
+    norm; stats = {"zeros", "penalised", "l1_term", "pg_norm"} of the final point and "zeros_trace", the zero
+    count after each iteration."""
+    p = owlqn_params(**kw)
+    cap = max(int(p.max_iters), 1)
+    trace = np.zeros(cap, np.int64)
+    p.zeros_trace = trace.ctypes.data_as(C.POINTER(C.c_longlong))
+    p.trace_cap = cap
+    hist = History(cap)
+    info = SolveInfo()
+    st = OwlqnStats()
+    n_local = int(X.shape[0])
+    check(lib().lbf_owlqn_solve(net.h, C.byref(p), ptr(params, numel=net.nparams), ptr(X), ptr(Y), n_local,
+                                int(n_global or n_local), C.byref(hist.rec), C.byref(info), C.byref(st)),
+          "lbf_owlqn_solve")
+    stats = {k: getattr(st, k) for k, _ in OwlqnStats._fields_}
+    stats["zeros_trace"] = trace[:int(info.iterations)]
+    return hist.as_dict(), info, stats
 
 
 def sgd_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, record: bool = True, **kw):

@@ -50,6 +50,8 @@ class UnifiedConfig:
                                  # like UnifiedLauncher.setLoss, and it then stays the network's loss)
     l2: float = 0.0              # weight decay of UnifiedLBFGS / UnifiedGD / UnifiedSGD (HIP extension; train()
                                  # applies a non-zero value like UnifiedLauncher.setL2, and it then stays)
+    l1: float = 0.0              # L1 penalty on the weights, UnifiedOWLQN only (HIP extension): the other optimisers
+                                 # do not read it
     curvature: str = "fd"        # UnifiedSLBFGS's curvature pairs (HIP extension): "fd" (the reference's finite
                                  # difference), "exact" (R-operator H s) or "gauss_newton" (G s, always y.s > 0)
     # UnifiedHF (HIP extension): CG iterations and relative residual per step, the initial damping, and the rows of
@@ -361,6 +363,26 @@ class UnifiedHF(UnifiedOptimizer):
         self.info = info
         self.history = hist
         self.traces = traces
+        return rec
+
+
+class UnifiedOWLQN(UnifiedOptimizer):
+    """L1-regularised L-BFGS (HIP extension, no reference counterpart): engine.owlqn_solve with the config's l1,
+    m_param, max_iters and tolerance; the loss and l2 are the network's. The recorded loss includes the penalties;
+    the zero counts are kept in self.stats."""
+
+    def optimize(self, net, data, config):
+        if config.eval_every > 0:
+            raise LbfError("UnifiedOWLQN has no resumable form: eval_every > 0 needs UnifiedLBFGS or UnifiedSLBFGS")
+        hist, info, stats = engine.owlqn_solve(net.mlp, net.params, data.x, data.y, n_global=data.n_global,
+                                               m=config.m_param, max_iters=config.max_iters, tol=config.tolerance,
+                                               l1=config.l1)
+        rec = IterationRecorder()
+        for i in range(len(hist["loss"])):
+            rec.record(i, float(hist["loss"][i]), float(hist["grad_norm"][i]), float(hist["time_ms"][i]))
+        self.info = info
+        self.history = hist
+        self.stats = stats
         return rec
 
 
