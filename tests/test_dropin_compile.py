@@ -138,3 +138,14 @@ def test_hip_backend_standalone_compiles(tmp_path):
     r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", f"-I{os.path.join(ROOT, 'include')}",
                         str(src)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-4000:]
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ missing")
+@pytest.mark.parametrize("driver", ["main_hip.cpp", "known_answer_hip.cpp", "parity_hip.cpp"])
+def test_drivers_compile(driver):
+    """The drivers over the standalone header (parity_hip.cpp: the HF / OWL-QN / metrics / cross-entropy calls),
+    checked where there is no GPU to run them on."""
+    src = os.path.join(ROOT, "lbfgs-ffnn_amd", "drivers", driver)
+    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", f"-I{os.path.join(ROOT, 'include')}", src],
+                       capture_output=True, text=True)
+    assert r.returncode == 0 and "warning" not in r.stderr, r.stderr[-4000:]
