@@ -414,6 +414,51 @@ void lbf_hf_default_params(lbf_hf_params *p);
 int lbf_hf_solve(lbf_mlp *net, const lbf_hf_params *prm, float *d_params, const float *d_X, const float *d_Y,
                  long long n_local, long long n_global, lbf_record *rec, lbf_solve_info *info);
 
+/* ---- Preconditioned Hessian-free (extension; Martens 2010, section 4.7). New functions and one new struct only:
+ * lbf_hf_params, lbf_cg_params and lbf_cg_info are unchanged and LBF_ABI_VERSION stays 3.
+ *
+ * lbf_mlp_grad_sq: d_out[i] = scale * sum_b (d l_b / d w_i)^2 over the batch rows (gathered through d_idx as
+ * everywhere), l_b row b's data loss at inv_scale = 1: 0.5 |a_b - y_b|^2 (LBF_LOSS_MSE) or sum_o y_bo (lse_b - z_bo)
+ * (LBF_LOSS_SOFTMAX_XENT). Flat parameter layout, no l2 term, every entry >= 0: the diagonal of the empirical Fisher
+ * matrix. No per-example gradient is stored: per layer one MFMA product of the squared operands over row chunks of
+ * the batch, the chunks' slabs summed in a fixed order (no atomics: two calls give equal bits). With a communicator
+ * every rank sums its own rows and the scaled vectors are all-reduced; batch == 0 is an empty share. It overwrites
+ * the network's activation workspace like lbf_mlp_forward. LBF_ERR_INVALID: null handles, batch < 0, scale negative
+ * or non-finite. Synchronises. */
+int lbf_mlp_grad_sq(lbf_mlp *net, const float *d_params, const float *d_X, const float *d_Y, const int *d_idx,
+                    long long batch, double scale, float *d_out);
+/* lbf_mlp_gn_pcg: lbf_mlp_gn_cg preconditioned with a diagonal. d_minv: parameter count floats, the INVERSE of the
+ * preconditioner's diagonal, every entry > 0 (not validated), 4-byte aligned. With z = minv .* r:
+ *   alpha = r.z / p.Ap;  x += alpha p;  r -= alpha Ap;  beta = r'.z' / r.z;  p = z' + beta p   (p_0 = z_0).
+ * z is never stored (the sweeps re-form it in registers): an iteration costs two more reads of the parameter count
+ * and no further launch. The stopping test stays rr <= rtol^2 rr0 on the recurrence residual, and rr0, rr, xb, xr,
+ * xx mean what they mean for lbf_mlp_gn_cg. Status 2 also covers a non-finite or non-positive r.z. With d_minv all
+ * ones the result (x, the residual and info) is bitwise lbf_mlp_gn_cg's. */
+int lbf_mlp_gn_pcg(lbf_mlp *net, const float *d_params, const float *d_b, const float *d_minv, const float *d_X,
+                   const float *d_Y, const int *d_idx, long long batch, double inv_scale, const lbf_cg_params *prm,
+                   float *d_x, lbf_cg_info *info);
+/* lbf_hf_solve_pc: lbf_hf_solve with a preconditioned step 2. pc NULL or mode LBF_PRECOND_NONE: lbf_hf_solve, bit
+ * for bit. Mode LBF_PRECOND_GRAD_SQ: step 2 becomes preconditioned CG (lbf_mlp_gn_pcg) on
+ * (G + (l2 + lambda_k) I) p = -g with
+ *   M_i = (cinv D_i + l2 + lambda_k)^exponent,   d_minv = 1 / M,
+ * D = lbf_mlp_grad_sq on that iteration's curvature rows (the curv_rows window, or all local rows; all-reduced over
+ * a communicator, so every rank holds the same M) and cinv the 1 / rows the CG uses, so M has the units of
+ * G + (l2 + lambda) I. D is recomputed when k % refresh == 0; M every iteration, because lambda_k moves. l2 +
+ * lambda_k must be > 0 (a parameter no row reaches has D_i = 0). Steps 1 and 3 to 6 are unchanged: they use x.b, x.r
+ * and x.x only. exponent == 0 gives M = 1 and the bits of lbf_hf_solve. LBF_ERR_INVALID: as lbf_hf_solve, an unknown
+ * mode, exponent outside [0, 1], refresh < 1. */
+#define LBF_PRECOND_NONE 0
+#define LBF_PRECOND_GRAD_SQ 1
+typedef struct lbf_hf_precond {
+  int mode;        /* LBF_PRECOND_NONE */
+  double exponent; /* 0.75 */
+  int refresh;     /* 1: outer iterations between two evaluations of D */
+} lbf_hf_precond;
+void lbf_hf_precond_default(lbf_hf_precond *p);
+int lbf_hf_solve_pc(lbf_mlp *net, const lbf_hf_params *prm, const lbf_hf_precond *pc, float *d_params,
+                    const float *d_X, const float *d_Y, long long n_local, long long n_global, lbf_record *rec,
+                    lbf_solve_info *info);
+
 /* ---- OWL-QN: L1-regularised L-BFGS (extension; Andrew & Gao 2007, libLBFGS's orthantwise_c). New functions and
  * structs only: LBF_ABI_VERSION stays 3.
  *

@@ -211,6 +211,12 @@ public:
     e.loss = r.rows > 0 ? r.loss * (1.0 / double(r.rows)) : 0.0; // linear in inv_scale: 1 / total rows
     return e;
   }
+  /// d_out[i] = scale * sum_b (d l_b / d w_i)^2 over `batch` rows (lbf_mlp_grad_sq): the sum of the squared
+  /// per-example gradients of the data loss, the diagonal of the empirical Fisher matrix, in the flat parameter
+  /// layout (parameter count floats on the device). No l2 term. Overwrites the activation workspace.
+  void gradSq(const HipScalar *d_x, const HipScalar *d_y, long long batch, double scale, HipScalar *d_out) {
+    hip_check(lbf_mlp_grad_sq(net_, params_.data(), d_x, d_y, nullptr, batch, scale, d_out), "lbf_mlp_grad_sq");
+  }
   lbf_mlp *raw() const { return net_; }
   HipHandle &handle() { return h_; }
   const std::vector<int> &dims() const { return dims_; }
@@ -402,6 +408,68 @@ private:
   HipNetwork &net_;
   int cg_iters_ = 50;
   double cg_rtol_ = 0.1, damping0_ = 1.0;
+  long long curv_rows_ = 0;
+};
+
+/// HipHF with the CG preconditioned by the squared-gradient diagonal (lbf_hf_solve_pc, LBF_PRECOND_GRAD_SQ):
+/// M = (D / rows + l2 + damping)^exponent, D = HipNetwork::gradSq of the curvature rows. A class of its own, so that
+/// a program using HipHF alone links against a library that predates lbf_hf_solve_pc.
+class HipHFPreconditioned : public HipMinimizerBase {
+public:
+  HipHFPreconditioned(HipHandle &handle, HipNetwork &net) : HipMinimizerBase(handle), net_(net) {}
+  void setCG(int iters, double rtol) {
+    cg_iters_ = iters;
+    cg_rtol_ = rtol;
+  }
+  void setDamping(double damping0) { damping0_ = damping0; }
+  void setCurvatureRows(long long rows) { curv_rows_ = rows; }
+  /// exponent in [0, 1] (0: no preconditioning, the bits of HipHF); refresh: outer iterations between two
+  /// evaluations of D
+  void setPreconditioner(double exponent, int refresh = 1) {
+    exponent_ = exponent;
+    refresh_ = refresh;
+  }
+
+  void solve(int n, HipScalar *params, const HipScalar *input, const HipScalar *target, int batch,
+             const LossGradFun &) override {
+    if (n <= 0 || params == nullptr) {
+      last_iterations_ = 0;
+      return;
+    }
+    lbf_hf_params prm;
+    lbf_hf_default_params(&prm);
+    prm.max_iters = max_iters_;
+    prm.tol = tol_;
+    prm.cg_iters = cg_iters_;
+    prm.cg_rtol = cg_rtol_;
+    prm.damping0 = damping0_;
+    prm.curv_rows = curv_rows_;
+    prm.max_line_iters = max_line_iters_;
+    prm.c1 = c1_;
+    prm.rho = rho_;
+    lbf_hf_precond pc;
+    lbf_hf_precond_default(&pc);
+    pc.mode = LBF_PRECOND_GRAD_SQ;
+    pc.exponent = exponent_;
+    pc.refresh = refresh_;
+    lbf_record rec{};
+    lbf_record *rp = nullptr;
+    if (recorder_) {
+      recorder_->reset();
+      rec = recorder_->view();
+      rp = &rec;
+    }
+    lbf_solve_info info{};
+    hip_check(lbf_hf_solve_pc(net_.raw(), &prm, &pc, params, input, target, batch, batch, rp, &info),
+              "lbf_hf_solve_pc");
+    if (recorder_) recorder_->set_size(rec.size);
+    last_iterations_ = info.iterations;
+  }
+
+private:
+  HipNetwork &net_;
+  int cg_iters_ = 50, refresh_ = 1;
+  double cg_rtol_ = 0.1, damping0_ = 1.0, exponent_ = 0.75;
   long long curv_rows_ = 0;
 };
 
@@ -693,6 +761,49 @@ public:
     recorder.set_size(rec.size);
     write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
   }
+};
+
+/// UnifiedHF_HIP with the CG preconditioned by the squared-gradient diagonal (lbf_hf_solve_pc); the exponent and the
+/// refresh interval are the optimizer's own (setPreconditioner), since the reference's UnifiedConfig has no place
+/// for them. A class of its own for the reason given at HipHFPreconditioned.
+class UnifiedHFPreconditioned_HIP : public UnifiedOptimizer<HipBackend> {
+public:
+  void setPreconditioner(double exponent, int refresh = 1) {
+    exponent_ = exponent;
+    refresh_ = refresh;
+  }
+  void optimize(hip_mlp::HipHandle &, NetworkWrapper<HipBackend> &net, const UnifiedDataset &host_data,
+                hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dx, hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dy,
+                const UnifiedConfig &c) override {
+    const long n_train = long(host_data.train_x.cols());
+    auto &nw = net.getInternal();
+    lbf_hf_params prm;
+    lbf_hf_default_params(&prm);
+    prm.max_iters = c.max_iters;
+    prm.tol = c.tolerance;
+#ifndef LBF_USE_REFERENCE_UNIFIED_TYPES // the reference's own UnifiedConfig has no such members
+    prm.cg_iters = c.cg_iters;
+    prm.cg_rtol = c.cg_rtol;
+    prm.damping0 = c.damping;
+#endif
+    lbf_hf_precond pc;
+    lbf_hf_precond_default(&pc);
+    pc.mode = LBF_PRECOND_GRAD_SQ;
+    pc.exponent = exponent_;
+    pc.refresh = refresh_;
+    recorder.init(c.max_iters);
+    lbf_record rec = recorder.view();
+    lbf_solve_info info{};
+    hip_mlp::hip_check(lbf_hf_solve_pc(nw.raw(), &prm, &pc, nw.params_data(), dx.data(), dy.data(), n_train, n_train,
+                                       &rec, &info),
+                       "lbf_hf_solve_pc");
+    recorder.set_size(rec.size);
+    write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
+  }
+
+private:
+  double exponent_ = 0.75;
+  int refresh_ = 1;
 };
 
 /// L1-regularised L-BFGS (HIP extension, no reference counterpart): lbf_owlqn_solve with the config's m_param,

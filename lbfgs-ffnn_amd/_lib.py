@@ -22,6 +22,7 @@ LS_WOLFE, LS_ARMIJO = 0, 1
 INIT_CPU, INIT_CUDA = 0, 1
 ACTS = {"linear": 0, "tanh": 1, "relu": 2, "sigmoid": 3}
 LOSSES = {"mse": 0, "softmax_xent": 1}  # LBF_LOSS_MSE, LBF_LOSS_SOFTMAX_XENT
+PRECONDS = {"none": 0, "grad_sq": 1}  # LBF_PRECOND_NONE, LBF_PRECOND_GRAD_SQ
 
 
 class LbfError(RuntimeError):
@@ -64,6 +65,10 @@ class HfParams(C.Structure):  # lbf_hf_params
                 ("ratio_lo", C.c_double), ("ratio_hi", C.c_double), ("c1", C.c_double), ("rho", C.c_double),
                 ("max_line_iters", C.c_int), ("curv_rows", C.c_longlong), ("damping_trace", C.POINTER(C.c_double)),
                 ("ratio_trace", C.POINTER(C.c_double)), ("cg_trace", C.POINTER(C.c_int)), ("trace_cap", C.c_int)]
+
+
+class HfPrecond(C.Structure):  # lbf_hf_precond
+    _fields_ = [("mode", C.c_int), ("exponent", C.c_double), ("refresh", C.c_int)]
 
 
 class OwlqnParams(C.Structure):  # lbf_owlqn_params
@@ -187,6 +192,12 @@ def lib():
         "lbf_hf_default_params": (None, [C.POINTER(HfParams)]),
         "lbf_hf_solve": (C.c_int, [_vp, C.POINTER(HfParams), _vp, _vp, _vp, C.c_longlong, C.c_longlong,
                                    C.POINTER(Record), C.POINTER(SolveInfo)]),
+        "lbf_mlp_grad_sq": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, _vp]),
+        "lbf_mlp_gn_pcg": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.POINTER(CgParams),
+                                     _vp, C.POINTER(CgInfo)]),
+        "lbf_hf_precond_default": (None, [C.POINTER(HfPrecond)]),
+        "lbf_hf_solve_pc": (C.c_int, [_vp, C.POINTER(HfParams), C.POINTER(HfPrecond), _vp, _vp, _vp, C.c_longlong,
+                                      C.c_longlong, C.POINTER(Record), C.POINTER(SolveInfo)]),
         "lbf_owlqn_default_params": (None, [C.POINTER(OwlqnParams)]),
         "lbf_owlqn_solve": (C.c_int, [_vp, C.POINTER(OwlqnParams), _vp, _vp, _vp, C.c_longlong, C.c_longlong,
                                       C.POINTER(Record), C.POINTER(SolveInfo), C.POINTER(OwlqnStats)]),
@@ -215,7 +226,16 @@ EXPORTS = ("lbf_last_error lbf_version lbf_abi_version lbf_ctx_create lbf_ctx_de
            "lbf_sgd_solve lbf_idx_read_images lbf_idx_read_labels lbf_mlp_hvp lbf_mlp_fd_hvp lbf_mlp_loss "
            "lbf_mlp_set_loss lbf_mlp_get_loss lbf_mlp_set_l2 lbf_mlp_get_l2 lbf_mlp_evaluate lbf_mlp_gnvp "
            "lbf_cg_default_params lbf_mlp_gn_cg lbf_mlp_gn_cg_residual lbf_hf_default_params lbf_hf_solve "
-           "lbf_owlqn_default_params lbf_owlqn_solve lbf_mlp_l1_pseudo_grad lbf_mlp_l1_trial").split()
+           "lbf_owlqn_default_params lbf_owlqn_solve lbf_mlp_l1_pseudo_grad lbf_mlp_l1_trial "
+           "lbf_mlp_grad_sq lbf_mlp_gn_pcg lbf_hf_precond_default lbf_hf_solve_pc").split()
+
+
+def check_precond(name) -> int:
+    """A preconditioner name of hf_solve ("none", "grad_sq") as its LBF_PRECOND_* code (checked before anything
+    touches the device)."""
+    if name not in PRECONDS:
+        raise LbfError(f"unknown preconditioner {name!r} (known: {', '.join(sorted(PRECONDS))})")
+    return PRECONDS[name]
 
 
 def check_l2(l2) -> float:

@@ -545,6 +545,39 @@ int lbf_mlp_gn_cg(lbf_mlp *net, const float *d_params, const float *d_b, const f
   });
 }
 
+int lbf_mlp_gn_pcg(lbf_mlp *net, const float *d_params, const float *d_b, const float *d_minv, const float *d_X,
+                   const float *d_Y, const int *d_idx, long long batch, double inv_scale, const lbf_cg_params *prm,
+                   float *d_x, lbf_cg_info *info) {
+  return guard([&] {
+    LBF_REQUIRE(net && prm && d_params && d_b && d_minv && d_x && batch >= 0 && (batch == 0 || (d_X && d_Y)),
+                "bad argument");
+    net->ctx->c.set_device();
+    Mlp::CgInfo ci;
+    net->net->gn_cg(d_params, d_b, 1.0f, d_X, d_Y, d_idx, batch, inv_scale, prm->damping, prm->max_iters, prm->rtol,
+                    prm->check, d_x, &ci, d_minv);
+    if (info) {
+      info->iterations = ci.iterations;
+      info->status = ci.status;
+      info->rr0 = ci.rr0;
+      info->rr = ci.rr;
+      info->xb = ci.xb;
+      info->xr = ci.xr;
+      info->xx = ci.xx;
+    }
+  });
+}
+
+int lbf_mlp_grad_sq(lbf_mlp *net, const float *d_params, const float *d_X, const float *d_Y, const int *d_idx,
+                    long long batch, double scale, float *d_out) {
+  return guard([&] {
+    LBF_REQUIRE(net && d_params && d_out && batch >= 0 && (batch == 0 || (d_X && d_Y)), "bad argument");
+    LBF_REQUIRE(std::isfinite(scale) && scale >= 0.0, "scale must be finite and >= 0");
+    net->ctx->c.set_device();
+    net->net->grad_sq(d_params, d_X, d_Y, d_idx, batch, scale, d_out);
+    LBF_HIP(hipStreamSynchronize(net->ctx->c.stream));
+  });
+}
+
 int lbf_mlp_gn_cg_residual(lbf_mlp *net, float *d_r) {
   return guard([&] {
     LBF_REQUIRE(net && d_r, "null argument");
@@ -580,6 +613,23 @@ int lbf_hf_solve(lbf_mlp *net, const lbf_hf_params *prm, float *d_params, const 
   return guard([&] {
     LBF_REQUIRE(net && prm, "null argument");
     run_hf(net->net.get(), *prm, d_params, d_X, d_Y, n_local, n_global, rec, info);
+  });
+}
+
+void lbf_hf_precond_default(lbf_hf_precond *p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->mode = LBF_PRECOND_NONE;
+  p->exponent = 0.75;
+  p->refresh = 1;
+}
+
+int lbf_hf_solve_pc(lbf_mlp *net, const lbf_hf_params *prm, const lbf_hf_precond *pc, float *d_params,
+                    const float *d_X, const float *d_Y, long long n_local, long long n_global, lbf_record *rec,
+                    lbf_solve_info *info) {
+  return guard([&] {
+    LBF_REQUIRE(net && prm, "null argument");
+    run_hf(net->net.get(), *prm, d_params, d_X, d_Y, n_local, n_global, rec, info, pc);
   });
 }
 

@@ -73,16 +73,28 @@ __device__ __forceinline__ bool block_aborted(const int *abort) {
 
 __device__ __forceinline__ bool finite_pos(double v) { return v > 0.0 && v <= 1.7976931348623157e308; }
 
+// PC (all three sweeps): preconditioned CG with the diagonal inverse preconditioner minv. z = minv .* r is formed
+// in registers wherever it is needed and never stored; rz holds the partials of r.z like rr those of r.r. With
+// minv == 1 every product 1 * r is exact and the r.z partials are the r.r partials in the same order, so the PC
+// sweeps then write the bits of the plain ones. The plain instantiations compile from the code they always did.
+template <bool PC>
 __global__ __launch_bounds__(256) void cg_init_kernel(Span sp, float *x, float *r, float *p, const float *b,
-                                                      float bscale, double *rr) {
+                                                      float bscale, double *rr, const float *minv, double *rz) {
   __shared__ double wv[4];
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
-  double q = 0.0;
+  double q = 0.0, qz = 0.0;
   for (long long v = gid; v < sp.nvec; v += stride) {
     const long long e = sp.head + 4 * v;
     const f32x4 bv = bscale * *reinterpret_cast<const f32x4 *>(b + e);
     *reinterpret_cast<f32x4 *>(r + e) = bv;
-    *reinterpret_cast<f32x4 *>(p + e) = bv;
+    if constexpr (PC) {
+      const f32x4 zv = *reinterpret_cast<const f32x4 *>(minv + e) * bv;
+      *reinterpret_cast<f32x4 *>(p + e) = zv;
+      qz += double(bv.x) * double(zv.x) + double(bv.y) * double(zv.y) + double(bv.z) * double(zv.z) +
+            double(bv.w) * double(zv.w);
+    } else {
+      *reinterpret_cast<f32x4 *>(p + e) = bv;
+    }
     *reinterpret_cast<f32x4 *>(x + e) = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     q += double(bv.x) * double(bv.x) + double(bv.y) * double(bv.y) + double(bv.z) * double(bv.z) +
          double(bv.w) * double(bv.w);
@@ -91,23 +103,36 @@ __global__ __launch_bounds__(256) void cg_init_kernel(Span sp, float *x, float *
     const long long e = span_elem(sp, j);
     const float bv = bscale * b[e];
     r[e] = bv;
-    p[e] = bv;
+    if constexpr (PC) {
+      const float zv = minv[e] * bv;
+      p[e] = zv;
+      qz += double(bv) * double(zv);
+    } else {
+      p[e] = bv;
+    }
     x[e] = 0.0f;
     q += double(bv) * double(bv);
   }
   q = block_sum_all(q, wv);
   if (threadIdx.x == 0) rr[blockIdx.x] = q;
+  if constexpr (PC) {
+    qz = block_sum_all(qz, wv);
+    if (threadIdx.x == 0) rz[blockIdx.x] = qz;
+  }
 }
 
 // One workgroup: rr0 and the first status block. b = 0 is solved by x = 0 in 0 iterations; a non-finite b
 // cannot be solved. Either way the abort word freezes the iterations enqueued behind this launch.
-__global__ __launch_bounds__(256) void cg_start_kernel(const double *rr, int nwg, double *st, int *abort) {
+// rz (PC only, else null): a non-finite or non-positive r.z of a non-zero b cannot start either.
+__global__ __launch_bounds__(256) void cg_start_kernel(const double *rr, int nwg, double *st, int *abort,
+                                                       const double *rz) {
   __shared__ double wv[4];
   const double rr0 = table_sum(rr, nwg, wv);
+  const double rz0 = rz ? table_sum(rz, nwg, wv) : 1.0;
   if (threadIdx.x != 0) return;
   int status = CG_RUNNING;
   if (rr0 == 0.0) status = CG_CONVERGED;
-  else if (!finite_pos(rr0)) status = CG_BREAKDOWN;
+  else if (!finite_pos(rr0) || !finite_pos(rz0)) status = CG_BREAKDOWN;
   st[CG_ITER] = 0.0;
   st[CG_RR] = rr0;
   st[CG_RR0] = rr0;
@@ -138,14 +163,23 @@ __global__ __launch_bounds__(256) void cg_pap_kernel(Span sp, const float *p, co
 
 // x += alpha p, r -= alpha Ap with alpha = float(rr_k / pAp); partials of the new r.r into table (k + 1) & 1.
 // pAp <= 0 or non-finite: no workgroup writes a vector, workgroup 0 records the breakdown.
+// PC: alpha = float(rz_k / pAp); partials of the new r.z (z = minv .* r) into table (k + 1) & 1 of rz as well. A
+// non-finite or non-positive rz_k is a breakdown like pAp's.
+template <bool PC>
 __global__ __launch_bounds__(256) void cg_step_kernel(Span sp, int k, float *x, float *r, const float *p,
                                                       const float *Ap, const double *pap, double *rr, int nwg,
-                                                      double *st, int *abort) {
+                                                      double *st, int *abort, const float *minv, double *rz) {
   __shared__ double wv[4];
   if (block_aborted(abort)) return;
   const double pAp = table_sum(pap, nwg, wv);
   const double rrk = table_sum(rr + size_t(k & 1) * nwg, nwg, wv);
-  if (!finite_pos(pAp)) {
+  double num = rrk;
+  bool bad = !finite_pos(pAp);
+  if constexpr (PC) {
+    num = table_sum(rz + size_t(k & 1) * nwg, nwg, wv);
+    bad = bad || !finite_pos(num);
+  }
+  if (bad) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
       st[CG_ITER] = double(k);
       st[CG_RR] = rrk;
@@ -154,9 +188,9 @@ __global__ __launch_bounds__(256) void cg_step_kernel(Span sp, int k, float *x, 
     }
     return;
   }
-  const float alpha = float(rrk / pAp);
+  const float alpha = float(num / pAp);
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
-  double q = 0.0;
+  double q = 0.0, qz = 0.0;
   for (long long v = gid; v < sp.nvec; v += stride) {
     const long long e = sp.head + 4 * v;
     const f32x4 pv = *reinterpret_cast<const f32x4 *>(p + e), av = *reinterpret_cast<const f32x4 *>(Ap + e);
@@ -173,6 +207,11 @@ __global__ __launch_bounds__(256) void cg_step_kernel(Span sp, int k, float *x, 
     *reinterpret_cast<f32x4 *>(r + e) = rv;
     q += double(rv.x) * double(rv.x) + double(rv.y) * double(rv.y) + double(rv.z) * double(rv.z) +
          double(rv.w) * double(rv.w);
+    if constexpr (PC) {
+      const f32x4 zv = *reinterpret_cast<const f32x4 *>(minv + e) * rv;
+      qz += double(rv.x) * double(zv.x) + double(rv.y) * double(zv.y) + double(rv.z) * double(zv.z) +
+            double(rv.w) * double(zv.w);
+    }
   }
   for (long long j = gid; j < span_nscalar(sp); j += stride) {
     const long long e = span_elem(sp, j);
@@ -180,24 +219,38 @@ __global__ __launch_bounds__(256) void cg_step_kernel(Span sp, int k, float *x, 
     const float rv = __builtin_fmaf(-alpha, Ap[e], r[e]);
     r[e] = rv;
     q += double(rv) * double(rv);
+    if constexpr (PC) qz += double(rv) * double(minv[e] * rv);
   }
   q = block_sum_all(q, wv);
   if (threadIdx.x == 0) rr[size_t((k + 1) & 1) * nwg + blockIdx.x] = q;
+  if constexpr (PC) {
+    qz = block_sum_all(qz, wv);
+    if (threadIdx.x == 0) rz[size_t((k + 1) & 1) * nwg + blockIdx.x] = qz;
+  }
 }
 
 // The stopping test on rr_{k+1}; p = r + beta p with beta = float(rr_{k+1} / rr_k) when the solve goes on.
 // On a stop no workgroup writes p; workgroup 0 writes the status block either way.
+// PC: the test is unchanged (on r.r); p = minv .* r + beta p with beta = float(rz_{k+1} / rz_k). A solve that would
+// go on with a non-finite or non-positive rz_{k+1} stops as a breakdown instead (x and r are the iterate's).
+template <bool PC>
 __global__ __launch_bounds__(256) void cg_dir_kernel(Span sp, int k, const float *r, float *p, const double *rr,
                                                      int nwg, double *st, int *abort, int max_iters,
-                                                     double tol2) {
+                                                     double tol2, const float *minv, const double *rz) {
   __shared__ double wv[4];
   if (block_aborted(abort)) return;
   const double rrn = table_sum(rr + size_t((k + 1) & 1) * nwg, nwg, wv);
   const double rrk = table_sum(rr + size_t(k & 1) * nwg, nwg, wv);
   const double rr0 = st[CG_RR0]; // written by cg_start, an earlier launch
+  double bn = rrn, bk = rrk;
+  if constexpr (PC) {
+    bn = table_sum(rz + size_t((k + 1) & 1) * nwg, nwg, wv);
+    bk = table_sum(rz + size_t(k & 1) * nwg, nwg, wv);
+  }
   int status = CG_RUNNING;
   if (rrn <= tol2 * rr0) status = CG_CONVERGED;
   else if (k + 1 >= max_iters) status = CG_MAXITER;
+  else if (PC && !finite_pos(bn)) status = CG_BREAKDOWN;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     st[CG_ITER] = double(k + 1);
     st[CG_RR] = rrn;
@@ -205,11 +258,12 @@ __global__ __launch_bounds__(256) void cg_dir_kernel(Span sp, int k, const float
     if (status != CG_RUNNING) *abort = 1;
   }
   if (status != CG_RUNNING) return;
-  const float beta = float(rrn / rrk);
+  const float beta = float(bn / bk);
   const long long gid = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
   for (long long v = gid; v < sp.nvec; v += stride) {
     const long long e = sp.head + 4 * v;
-    const f32x4 rv = *reinterpret_cast<const f32x4 *>(r + e);
+    f32x4 rv = *reinterpret_cast<const f32x4 *>(r + e);
+    if constexpr (PC) rv = *reinterpret_cast<const f32x4 *>(minv + e) * rv;
     f32x4 pv = *reinterpret_cast<f32x4 *>(p + e);
     pv.x = __builtin_fmaf(beta, pv.x, rv.x);
     pv.y = __builtin_fmaf(beta, pv.y, rv.y);
@@ -219,8 +273,17 @@ __global__ __launch_bounds__(256) void cg_dir_kernel(Span sp, int k, const float
   }
   for (long long j = gid; j < span_nscalar(sp); j += stride) {
     const long long e = span_elem(sp, j);
-    p[e] = __builtin_fmaf(beta, p[e], r[e]);
+    float rv = r[e];
+    if constexpr (PC) rv = minv[e] * rv;
+    p[e] = __builtin_fmaf(beta, p[e], rv);
   }
+}
+
+// minv = (d + kappa)^(-alpha): the inverse of the diagonal preconditioner (d + kappa)^alpha. alpha == 0 gives ones.
+__global__ __launch_bounds__(256) void precond_minv_kernel(long long n, const float *d, float kappa, float alpha,
+                                                           float *minv) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e < n) minv[e] = powf(d[e] + kappa, -alpha);
 }
 
 // Partials of x.(bscale b), x.r, x.x: tables 0, 1, 2 of xd.
@@ -272,10 +335,15 @@ int cg_nwg(long long n) { return int(std::max(1LL, std::min<long long>(cdiv(n, 1
 
 void cg_init(hipStream_t s, const CgArgs &a) {
   const int nwg = cg_nwg(a.n);
-  hipLaunchKernelGGL(cg_init_kernel, dim3(unsigned(nwg)), dim3(256), 0, s, make_span(a.n, a.x, a.r, a.p, a.b), a.x,
-                     a.r, a.p, a.b, a.bscale, a.rr);
+  if (a.minv)
+    hipLaunchKernelGGL(cg_init_kernel<true>, dim3(unsigned(nwg)), dim3(256), 0, s,
+                       make_span(a.n, a.x, a.r, a.p, a.b, a.minv), a.x, a.r, a.p, a.b, a.bscale, a.rr, a.minv, a.rz);
+  else
+    hipLaunchKernelGGL(cg_init_kernel<false>, dim3(unsigned(nwg)), dim3(256), 0, s,
+                       make_span(a.n, a.x, a.r, a.p, a.b), a.x, a.r, a.p, a.b, a.bscale, a.rr, nullptr, nullptr);
   LBF_KERNEL_CHECK();
-  hipLaunchKernelGGL(cg_start_kernel, dim3(1), dim3(256), 0, s, a.rr, nwg, a.st, a.abort);
+  hipLaunchKernelGGL(cg_start_kernel, dim3(1), dim3(256), 0, s, a.rr, nwg, a.st, a.abort,
+                     a.minv ? (const double *)a.rz : nullptr);
   LBF_KERNEL_CHECK();
 }
 
@@ -287,15 +355,25 @@ void cg_pap(hipStream_t s, const CgArgs &a) {
 
 void cg_step(hipStream_t s, const CgArgs &a, int k) {
   const int nwg = cg_nwg(a.n);
-  hipLaunchKernelGGL(cg_step_kernel, dim3(unsigned(nwg)), dim3(256), 0, s, make_span(a.n, a.x, a.r, a.p, a.Ap), k,
-                     a.x, a.r, a.p, a.Ap, a.pap, a.rr, nwg, a.st, a.abort);
+  if (a.minv)
+    hipLaunchKernelGGL(cg_step_kernel<true>, dim3(unsigned(nwg)), dim3(256), 0, s,
+                       make_span(a.n, a.x, a.r, a.p, a.Ap, a.minv), k, a.x, a.r, a.p, a.Ap, a.pap, a.rr, nwg, a.st,
+                       a.abort, a.minv, a.rz);
+  else
+    hipLaunchKernelGGL(cg_step_kernel<false>, dim3(unsigned(nwg)), dim3(256), 0, s,
+                       make_span(a.n, a.x, a.r, a.p, a.Ap), k, a.x, a.r, a.p, a.Ap, a.pap, a.rr, nwg, a.st, a.abort,
+                       nullptr, nullptr);
   LBF_KERNEL_CHECK();
 }
 
 void cg_dir(hipStream_t s, const CgArgs &a, int k) {
   const int nwg = cg_nwg(a.n);
-  hipLaunchKernelGGL(cg_dir_kernel, dim3(unsigned(nwg)), dim3(256), 0, s, make_span(a.n, a.r, a.p), k, a.r, a.p,
-                     a.rr, nwg, a.st, a.abort, a.max_iters, a.tol2);
+  if (a.minv)
+    hipLaunchKernelGGL(cg_dir_kernel<true>, dim3(unsigned(nwg)), dim3(256), 0, s, make_span(a.n, a.r, a.p, a.minv), k,
+                       a.r, a.p, a.rr, nwg, a.st, a.abort, a.max_iters, a.tol2, a.minv, (const double *)a.rz);
+  else
+    hipLaunchKernelGGL(cg_dir_kernel<false>, dim3(unsigned(nwg)), dim3(256), 0, s, make_span(a.n, a.r, a.p), k, a.r,
+                       a.p, a.rr, nwg, a.st, a.abort, a.max_iters, a.tol2, nullptr, nullptr);
   LBF_KERNEL_CHECK();
 }
 
@@ -305,6 +383,13 @@ void cg_xdots(hipStream_t s, const CgArgs &a) {
                      a.b, a.bscale, a.xd, nwg);
   LBF_KERNEL_CHECK();
   hipLaunchKernelGGL(cg_xfin_kernel, dim3(1), dim3(256), 0, s, a.xd, nwg, a.st);
+  LBF_KERNEL_CHECK();
+}
+
+void precond_minv(hipStream_t s, long long n, const float *d, double kappa, double alpha, float *minv) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(precond_minv_kernel, dim3(unsigned(cdiv(n, 256))), dim3(256), 0, s, n, d, float(kappa),
+                     float(alpha), minv);
   LBF_KERNEL_CHECK();
 }
 

@@ -209,7 +209,16 @@ void rowhead(hipStream_t s, const RowHeadArgs &a);
 void fwd_reduce_act(hipStream_t s, const float *slab, int splits, long long stride, int M, int N, const float *bias,
                     int act, float *out, const int *abort);
 void reduce_slabs(hipStream_t s, const float *slab, int splits, long long stride, long long count, float *grad,
-                  const int *abort = nullptr);
+                  const int *abort = nullptr, double scale = 1.0);
+
+// Sum of squared per-example gradients of one dense layer (fisher.hip; the pass is Mlp::grad_sq):
+//   out[i * Out + j] = scale * sum_b a_{bi}^2 d_{bj}^2, i <= In (row In: the bias, a = 1), j < Out,
+// A [B][In] (rows gathered through idx when non-null), D [B][Out] the layer's deltas at inv_scale = 1. The batch is
+// cut into grad_sq_splits(B, In, Out) row chunks, one partial slab of (In + 1) * Out floats each in `slab`, summed
+// in chunk order by reduce_slabs, which applies scale: no atomics, the same bits on every call.
+int grad_sq_splits(long long B, int In, int Out, long long *chunk = nullptr);
+void grad_sq_layer(hipStream_t s, const float *A, int In, const int *idx, const float *D, int Out, long long B,
+                   double scale, float *slab, float *out);
 
 // g += lambda*w (if lambda != 0); per-WG partials of (g.g, g.p, w.w) -> partials[wg*3 + {0,1,2}]
 int dots_partials_wg(long long n);
@@ -307,7 +316,15 @@ struct CgArgs {
   int *abort = nullptr;      // the solver's abort word
   int max_iters = 0;
   double tol2 = 0.0;         // rtol^2
+  // Preconditioned CG (minv non-null): the inverse of a diagonal preconditioner, entries > 0. With z = minv .* r:
+  // alpha = r.z / p.Ap, beta = r'.z' / r.z, p = z' + beta p; the stopping test stays on r.r. z is never stored:
+  // cg_step and cg_dir re-form it in registers. A non-finite or non-positive r.z is a breakdown (CG_BREAKDOWN).
+  // minv == 1 everywhere gives the bits of the plain solve.
+  const float *minv = nullptr;
+  double *rz = nullptr;      // [2][cg_nwg(n)] partials of r.z, the parities of rr
 };
+// minv[i] = (d[i] + kappa)^(-alpha) (powf): the inverse of the preconditioner (d + kappa)^alpha; alpha == 0: ones
+void precond_minv(hipStream_t s, long long n, const float *d, double kappa, double alpha, float *minv);
 // x = 0, r = p = bscale b, table 0 of r.r; then one workgroup: rr0, and a zero or non-finite rr0 stops at once
 void cg_init(hipStream_t s, const CgArgs &a);
 void cg_pap(hipStream_t s, const CgArgs &a);

@@ -1269,6 +1269,36 @@ void Mlp::gn_apply(const float *P, const float *V, const float *X, const float *
 }
 
 // ------------------------------------------------------------------------------------------------
+// Sum of squared per-example gradients (fisher.hip): the plain backward pass of hvp with the [dW ; db]
+// GEMM replaced by the squared product. The deltas are taken at inv_scale = 1 and the scale is applied where the
+// slabs are summed: squares of deltas pre-scaled by 1 / 60000 would sit needlessly close to the fp32 denormals.
+// ------------------------------------------------------------------------------------------------
+void Mlp::grad_sq(const float *P, const float *X, const float *Y, const int *idx, long long B, double scale,
+                  float *out) {
+  LBF_REQUIRE(P && out && B >= 0 && (B == 0 || (X && Y)), "grad_sq: bad argument");
+  LBF_REQUIRE(std::isfinite(scale) && scale >= 0.0, "grad_sq: scale must be finite and >= 0");
+  hipStream_t s = ctx_->stream;
+  const int nl = int(layers_.size());
+  if (B == 0) { // a data-parallel rank with an empty share still joins the all-reduce
+    LBF_HIP(hipMemsetAsync(out, 0, nparams_ * sizeof(float), s));
+    if (ctx_->dp()) ctx_->allreduce(out, nparams_);
+    return;
+  }
+  gn_prepare(P, X, Y, idx, B);
+  size_t slab = 1;
+  for (const Layer &L : layers_) slab = std::max(slab, size_t(grad_sq_splits(B, L.in, L.out)) * size_t(L.in + 1) * L.out);
+  gsq_slab_.ensure(slab);
+  out_loss(Y, idx, B, 1.0);
+  for (int l = nl - 1; l >= 0; --l) {
+    const Layer &L = layers_[size_t(l)];
+    grad_sq_layer(s, l == 0 ? X : A_[size_t(l - 1)].get(), L.in, l == 0 ? idx : nullptr, D_[size_t(l)].get(), L.out, B,
+                  scale, gsq_slab_.get(), out + L.off);
+    if (l > 0) rpass_back_prod(B, l, D_[size_t(l)].get(), P, layers_[size_t(l - 1)].act, D_[size_t(l - 1)].get());
+  }
+  if (ctx_->dp()) ctx_->allreduce(out, nparams_);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Gauss-Newton conjugate gradients (cg.hip). Every launch of an iteration takes the solver's abort
 // word through ctx_->abort, so the iterations enqueued past the stopping one change nothing: x, r and the status
 // block stay bitwise what the stopping iteration left, whatever `check` is. Under a communicator a frozen
@@ -1277,7 +1307,7 @@ void Mlp::gn_apply(const float *P, const float *V, const float *X, const float *
 // ------------------------------------------------------------------------------------------------
 void Mlp::gn_cg(const float *P, const float *b, float bscale, const float *X, const float *Y, const int *idx,
                 long long B, double inv_scale, double damping, int max_iters, double rtol, int check, float *x,
-                CgInfo *info) {
+                CgInfo *info, const float *minv) {
   LBF_REQUIRE(P && b && x && B >= 0 && (B == 0 || (X && Y)), "gn_cg: bad argument");
   LBF_REQUIRE(max_iters >= 0 && rtol >= 0.0 && check >= 1, "gn_cg: max_iters >= 0, rtol >= 0, check >= 1");
   hipStream_t s = ctx_->stream;
@@ -1286,7 +1316,7 @@ void Mlp::gn_cg(const float *P, const float *b, float bscale, const float *X, co
   cg_r_.ensure(size_t(n));
   cg_p_.ensure(size_t(n));
   cg_ap_.ensure(size_t(n));
-  cg_part_.ensure(size_t(6) * size_t(nwg));
+  cg_part_.ensure(size_t(8) * size_t(nwg));
   cg_st_.ensure(CG_N);
   cg_abort_.ensure(1);
   cg_hst_.ensure(CG_N);
@@ -1301,6 +1331,8 @@ void Mlp::gn_cg(const float *P, const float *b, float bscale, const float *X, co
   a.pap = cg_part_.get();
   a.rr = cg_part_.get() + nwg;
   a.xd = cg_part_.get() + 3 * size_t(nwg);
+  a.minv = minv;
+  a.rz = cg_part_.get() + 6 * size_t(nwg);
   a.st = cg_st_.get();
   a.abort = cg_abort_.get();
   a.max_iters = max_iters;

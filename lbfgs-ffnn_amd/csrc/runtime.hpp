@@ -195,9 +195,19 @@ public:
     int iterations = 0, status = 0; // CG_CONVERGED / CG_MAXITER / CG_BREAKDOWN
     double rr0 = 0.0, rr = 0.0, xb = 0.0, xr = 0.0, xx = 0.0; // xb = x.(bscale b)
   };
+  // minv (nullable; nparams() floats, entries > 0, any 4-byte aligned pointer): preconditioned CG with the diagonal
+  // inverse preconditioner minv (kernels.hpp CgArgs): two more reads of n floats per iteration, no extra launch.
   void gn_cg(const float *P, const float *b, float bscale, const float *X, const float *Y, const int *idx,
              long long B, double inv_scale, double damping, int max_iters, double rtol, int check, float *x,
-             CgInfo *info);
+             CgInfo *info, const float *minv = nullptr);
+  // out[i] = scale * sum_b (d l_b / d w_i)^2 over the batch rows, l_b row b's data loss at inv_scale = 1
+  // (0.5 |a_b - y_b|^2, or sum_o y_bo (lse_b - z_bo)); flat parameter layout, no l2 term: the diagonal of the
+  // empirical Fisher matrix (fisher.hip). gn_prepare's unfused forward, out_loss at inv_scale = 1,
+  // then per layer from the top the squared product on (A_{l-1}, D_l) and the EPI_DX GEMM to D_{l-1}; scale is
+  // applied where the row chunks' slabs are summed. With a communicator every rank sums its rows, scales, and the
+  // scaled vectors are all-reduced once; B == 0 contributes zeros and joins. Overwrites the activation workspace
+  // like forward(). Bitwise reproducible.
+  void grad_sq(const float *P, const float *X, const float *Y, const int *idx, long long B, double scale, float *out);
   const float *cg_residual() const { return cg_r_.get(); } // r of the last gn_cg (null before the first)
   // Device-side evaluation (metrics.hip; replaces the host scan of unified_launcher.hpp:154-199): forward() and
   // the metrics kernel per chunk of chunk_rows rows (0: 65536, or the batch if smaller), so the activation
@@ -272,16 +282,17 @@ private:
   // R-pass workspace (hvp, gnvp): R{Z}, R{A}, R{dZ} and delta per layer, two products, one segment
   std::vector<DevBuf<float>> RZ_, RA_, RD_, DL_;
   DevBuf<float> T1_, T2_, seg_;
+  DevBuf<float> gsq_slab_; // grad_sq: the row chunks' partial slabs of one layer
   long long rcap_ = -1;
   void rpass_ensure(long long B); // grows the workspace to B rows
   // gnvp in two steps. gn_prepare: the workspaces and the unfused forward pass of the batch. gn_apply: the
   // R-forward, the loss's Hessian, the backward pass, the all-reduce and + lambda V, on the activations
   // gn_prepare left. The prepared state holds until the next call that writes the activation workspace (forward,
-  // loss_grad, loss_only, evaluate, hvp, gnvp); P, X, Y, idx and B must be gn_prepare's.
+  // loss_grad, loss_only, evaluate, hvp, gnvp, grad_sq); P, X, Y, idx and B must be gn_prepare's.
   void gn_prepare(const float *P, const float *X, const float *Y, const int *idx, long long B);
   void gn_apply(const float *P, const float *V, const float *X, const float *Y, const int *idx, long long B,
                 double inv_scale, double lambda, float *Gv);
-  // gn_cg's state: r, p, Ap, the partial tables [pap | rr x 2 | xdots x 3], the status block, the abort word
+  // gn_cg's state: r, p, Ap, the partial tables [pap | rr x 2 | xdots x 3 | rz x 2], the status block, the abort word
   DevBuf<float> cg_r_, cg_p_, cg_ap_;
   DevBuf<double> cg_part_, cg_st_;
   DevBuf<int> cg_abort_;

@@ -1419,8 +1419,12 @@ int run_sgd(Mlp *net, const lbf_sgd_params &prm, float *d_params, const float *X
 // status block per `cg_check` CG iterations and one loss per line-search trial. Every decision is taken on the
 // host from fp64 words that are all-reduced (or replicated) under a communicator, so the ranks agree.
 // ================================================================================================
+// Preconditioned (pc, mode LBF_PRECOND_GRAD_SQ): D = sum of squared per-example gradients of the
+// curvature rows (Mlp::grad_sq, all-reduced, refreshed every pc->refresh iterations), minv = (cinv D + l2 +
+// lambda_k)^(-exponent) every iteration, and the CG is Mlp::gn_cg's preconditioned form. Nothing else changes: q,
+// the ratio, the damping rule and the line search use x.b, x.r and x.x only.
 int run_hf(Mlp *net, const lbf_hf_params &prm, float *d_params, const float *X, const float *Y, long long n_local,
-           long long n_global, lbf_record *rec, lbf_solve_info *info) {
+           long long n_global, lbf_record *rec, lbf_solve_info *info, const lbf_hf_precond *pc) {
   LBF_REQUIRE(d_params && n_local >= 0 && n_global > 0 && (n_local == 0 || (X && Y)), "bad argument");
   LBF_REQUIRE(prm.max_iters >= 0 && prm.cg_iters >= 0 && prm.cg_rtol >= 0.0 && prm.cg_check >= 1 &&
                   prm.max_line_iters >= 1 && prm.damping0 >= 0.0 && prm.rho > 0.0 && prm.rho < 1.0,
@@ -1428,6 +1432,12 @@ int run_hf(Mlp *net, const lbf_hf_params &prm, float *d_params, const float *X, 
   Ctx *c = net->ctx();
   LBF_REQUIRE(prm.curv_rows >= 0 && prm.curv_rows <= n_local, "hf: curv_rows must lie in [0, n_local]");
   LBF_REQUIRE(prm.curv_rows == 0 || !c->comm, "hf: curv_rows > 0 runs on one rank (the window has no shard split)");
+  if (pc) {
+    LBF_REQUIRE(pc->mode == LBF_PRECOND_NONE || pc->mode == LBF_PRECOND_GRAD_SQ, "hf: unknown preconditioner mode");
+    LBF_REQUIRE(pc->exponent >= 0.0 && pc->exponent <= 1.0, "hf: preconditioner exponent must lie in [0, 1]");
+    LBF_REQUIRE(pc->refresh >= 1, "hf: preconditioner refresh must be >= 1");
+  }
+  const bool pcon = pc && pc->mode == LBF_PRECOND_GRAD_SQ;
   c->set_device();
   hipStream_t s = c->stream;
   const long long n = (long long)net->nparams();
@@ -1435,6 +1445,7 @@ int run_hf(Mlp *net, const lbf_hf_params &prm, float *d_params, const float *X, 
   const int nww = ww_partials_n(n);
   DevBuf<float> g(size_t(round4(n + 2))), p(size_t(std::max(1LL, n))), trial(size_t(std::max(1LL, n)));
   DevBuf<double> scal(SC_N), wwp{size_t(nww)};
+  DevBuf<float> dsq(size_t(pcon ? std::max(1LL, n) : 0)), minv(size_t(pcon ? std::max(1LL, n) : 0));
   PinnedBuf<double> hs;
   hs.ensure(SC_N);
   const long long evals0 = net->evals(), rows0 = net->rows(), lo0 = net->loss_only_evals();
@@ -1466,8 +1477,12 @@ int run_hf(Mlp *net, const lbf_hf_params &prm, float *d_params, const float *X, 
       cinv = 1.0 / double(prm.curv_rows);
     }
     Mlp::CgInfo ci;
+    if (pcon) {
+      if (it % pc->refresh == 0) net->grad_sq(d_params, Xc, Yc, nullptr, Bc, cinv, dsq.get());
+      precond_minv(s, n, dsq.get(), l2 + lam, pc->exponent, minv.get());
+    }
     net->gn_cg(d_params, g.get(), -1.0f, Xc, Yc, nullptr, Bc, cinv, l2 + lam, prm.cg_iters, prm.cg_rtol, prm.cg_check,
-               p.get(), &ci);
+               p.get(), &ci, pcon ? minv.get() : nullptr);
     const double q = -0.5 * (ci.xb + ci.xr) - 0.5 * lam * ci.xx; // g.p + 0.5 p^T (G + l2 I) p
     const double gp = -ci.xb;
     // ---- backtracking on the full objective ----

@@ -344,8 +344,10 @@ int run_sgd(Mlp *net, const lbf_sgd_params &prm, float *d_params, const float *X
 
 // Hessian-free solver (lbfgs_amd.h lbf_hf_solve): Gauss-Newton CG steps with Levenberg-Marquardt
 // damping and a backtracking line search; returns the outer iterations done.
+// pc (nullable; null or mode LBF_PRECOND_NONE: plain CG): the CG is preconditioned with
+// M = (cinv D + l2 + lambda_k)^exponent, D = Mlp::grad_sq of the curvature rows (lbf_hf_solve_pc).
 int run_hf(Mlp *net, const lbf_hf_params &prm, float *d_params, const float *X, const float *Y, long long n_local,
-           long long n_global, lbf_record *rec, lbf_solve_info *info);
+           long long n_global, lbf_record *rec, lbf_solve_info *info, const lbf_hf_precond *pc = nullptr);
 
 // OWL-QN (lbfgs_amd.h lbf_owlqn_solve): L-BFGS on loss + 0.5 l2 |w|^2 + l1 |w|_1 with the pseudo-gradient,
 // the sign-constrained direction and the orthant projection of Andrew & Gao 2007; returns the iterations done.

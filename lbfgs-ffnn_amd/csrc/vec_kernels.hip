@@ -189,7 +189,8 @@ void loss_xent(hipStream_t s, const float *Z, long long ldz_in, const float *Y, 
 // a fixed order. CW = 64 for few splits (coalesced 256-B rows), 16 when splits are many (more
 // parallelism per column for the tall-and-thin slabs of small layers).
 __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float *slab, int splits, long long stride,
-                                                           long long count, int cw, float *grad, const int *abort) {
+                                                           long long count, int cw, float *grad, const int *abort,
+                                                           double scale) {
   if (abort && *abort) return;
   __shared__ double part[256];
   const int t = threadIdx.x;
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float *slab, in
   if (stripe == 0 && col < count) {
     double r = 0.0;
     for (int q = 0; q < nst; ++q) r += part[q * cw + t];
-    grad[col] = float(r);
+    grad[col] = float(r * scale); // scale == 1: exact
   }
 }
 
@@ -238,10 +239,10 @@ void fwd_reduce_act(hipStream_t s, const float *slab, int splits, long long stri
 }
 
 void reduce_slabs(hipStream_t s, const float *slab, int splits, long long stride, long long count, float *grad,
-                  const int *abort) {
+                  const int *abort, double scale) {
   const int cw = splits > 64 ? 16 : 64;
   hipLaunchKernelGGL(reduce_slabs_kernel, dim3(unsigned(cdiv(count, cw))), dim3(256), 0, s, slab, splits, stride,
-                     count, cw, grad, abort);
+                     count, cw, grad, abort, scale);
   LBF_KERNEL_CHECK();
 }
 

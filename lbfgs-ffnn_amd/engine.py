@@ -14,7 +14,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import (ACTS, HVP_MODES, INIT_CPU, INIT_CUDA, LOSSES, check_l2, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED, SLBFGS_DP_SLICED,
+from ._lib import (ACTS, HVP_MODES, INIT_CPU, INIT_CUDA, LOSSES, PRECONDS, HfPrecond, check_l2, check_precond, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED, SLBFGS_DP_SLICED,
                    CgInfo, CgParams, EvalResultC, GdParams, HfParams, LbfError, LbfgsParams, OwlqnParams, OwlqnStats, Record, SgdParams, SlbfgsParams, SolveInfo, check, lib,
                    ptr)
 
@@ -376,6 +376,53 @@ class Mlp:
             info["r"] = r
         return out, info
 
+    def gn_pcg(self, params: torch.Tensor, b: torch.Tensor, minv: torch.Tensor, X: torch.Tensor, Y: torch.Tensor,
+               idx: Optional[torch.Tensor] = None, inv_scale: Optional[float] = None, l2: float = 0.0,
+               damping: Optional[float] = None, max_iters: Optional[int] = None, rtol: Optional[float] = None,
+               check: Optional[int] = None, out: Optional[torch.Tensor] = None, residual: bool = False):
+        """gn_cg preconditioned with a diagonal (lbf_mlp_gn_pcg): `minv` holds the inverse of the preconditioner's
+        diagonal, one entry > 0 per parameter. z = minv * r is never stored; the stopping test stays on r.r; status 2
+        also covers a non-positive r.z. With minv all ones the result is bitwise gn_cg's. Other arguments and the
+        return value as gn_cg."""
+        B = int(idx.numel()) if idx is not None else int(X.shape[0])
+        if inv_scale is None:
+            inv_scale = 1.0 / max(B, 1)
+        out = self.new_params() if out is None else out
+        self._check_data(X, Y)
+        n = self.nparams
+        p = CgParams()
+        lib().lbf_cg_default_params(C.byref(p))
+        p.damping = float(l2) + (0.0 if damping is None else float(damping))
+        for k, v in (("max_iters", max_iters), ("rtol", rtol), ("check", check)):
+            if v is not None:
+                setattr(p, k, v)
+        ci = CgInfo()
+        _check_rc(lib().lbf_mlp_gn_pcg(self.h, ptr(params, numel=n), ptr(b, numel=n), ptr(minv, numel=n), ptr(X),
+                                       ptr(Y), ptr(idx, torch.int32), B, inv_scale, C.byref(p), ptr(out, numel=n),
+                                       C.byref(ci)), "lbf_mlp_gn_pcg")
+        info = {k: getattr(ci, k) for k, _ in CgInfo._fields_}
+        if residual:
+            r = torch.empty(n, dtype=torch.float32, device=out.device)
+            _check_rc(lib().lbf_mlp_gn_cg_residual(self.h, ptr(r, numel=n)), "lbf_mlp_gn_cg_residual")
+            info["r"] = r
+        return out, info
+
+    def grad_sq(self, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, idx: Optional[torch.Tensor] = None,
+                scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """scale * sum_b (d l_b / d w)^2 over the batch rows (lbf_mlp_grad_sq): the sum of the squared per-example
+        gradients of the data loss (l_b at inv_scale = 1, no l2 term), i.e. the diagonal of the empirical Fisher
+        matrix, formed on the device without materialising a per-example gradient. scale defaults to 1 / rows.
+        Bitwise reproducible; with a communicator the ranks' scaled sums are all-reduced."""
+        B = int(idx.numel()) if idx is not None else int(X.shape[0])
+        if scale is None:
+            scale = 1.0 / max(B, 1)
+        out = self.new_params() if out is None else out
+        self._check_data(X, Y)
+        n = self.nparams
+        _check_rc(lib().lbf_mlp_grad_sq(self.h, ptr(params, numel=n), ptr(X), ptr(Y), ptr(idx, torch.int32), B,
+                                        float(scale), ptr(out, numel=n)), "lbf_mlp_grad_sq")
+        return out
+
     def l1_pseudo_grad(self, x: torch.Tensor, g: torch.Tensor, l1: float, l1_bias: bool = False,
                        out: Optional[torch.Tensor] = None):
         """OWL-QN's pseudo-gradient of f + l1 |w|_1 at x with smooth gradient g (lbf_mlp_l1_pseudo_grad): the
@@ -672,11 +719,30 @@ def hf_params(**kw) -> HfParams:
     return p
 
 
+def hf_precond(precond: str = "none", exponent: float = 0.75, refresh: int = 1) -> HfPrecond:
+    """lbf_hf_precond from a preconditioner name ("none", "grad_sq"), its exponent in [0, 1] and the outer iterations
+    between two evaluations of the squared-gradient diagonal. Raises LbfError without touching the library."""
+    pc = HfPrecond()
+    pc.mode = check_precond(precond)
+    if not (0.0 <= float(exponent) <= 1.0):
+        raise LbfError(f"precond_exponent must lie in [0, 1], got {exponent!r}")
+    if int(refresh) < 1:
+        raise LbfError(f"precond_refresh must be >= 1, got {refresh!r}")
+    pc.exponent = float(exponent)
+    pc.refresh = int(refresh)
+    return pc
+
+
 def hf_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, n_global: Optional[int] = None,
-             **kw):
+             precond: Optional[str] = None, precond_exponent: float = 0.75, precond_refresh: int = 1, **kw):
     """Hessian-free solver (lbf_hf_solve): Gauss-Newton CG steps with Levenberg-Marquardt damping and a
     backtracking line search on the network's loss + its l2; params updated in place. kw: see hf_params.
+    precond="grad_sq" (lbf_hf_solve_pc): the CG is preconditioned with M = (D / rows + l2 + damping)^precond_exponent,
+    D the sum of squared per-example gradients of the curvature rows (Mlp.grad_sq), re-evaluated every
+    precond_refresh outer iterations; precond="none" goes through lbf_hf_solve_pc too and gives the bits of the
+    default (None: lbf_hf_solve itself). An unknown name raises LbfError before the device is touched.
     Returns (hist, info, traces): traces = {"damping", "ratio", "cg"}, one entry per outer iteration."""
+    pc = None if precond is None else hf_precond(precond, precond_exponent, precond_refresh)
     p = hf_params(**kw)
     cap = max(int(p.max_iters), 1)
     damping, ratio, cg = np.full(cap, np.nan), np.full(cap, np.nan), np.zeros(cap, np.int32)
@@ -687,8 +753,12 @@ def hf_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, n
     hist = History(cap)
     info = SolveInfo()
     n_local = int(X.shape[0])
-    check(lib().lbf_hf_solve(net.h, C.byref(p), ptr(params), ptr(X), ptr(Y), n_local, int(n_global or n_local),
-                             C.byref(hist.rec), C.byref(info)), "lbf_hf_solve")
+    if pc is None:
+        check(lib().lbf_hf_solve(net.h, C.byref(p), ptr(params), ptr(X), ptr(Y), n_local, int(n_global or n_local),
+                                 C.byref(hist.rec), C.byref(info)), "lbf_hf_solve")
+    else:
+        check(lib().lbf_hf_solve_pc(net.h, C.byref(p), C.byref(pc), ptr(params), ptr(X), ptr(Y), n_local,
+                                    int(n_global or n_local), C.byref(hist.rec), C.byref(info)), "lbf_hf_solve_pc")
     k = int(info.iterations)
     return hist.as_dict(), info, {"damping": damping[:k], "ratio": ratio[:k], "cg": cg[:k]}
 

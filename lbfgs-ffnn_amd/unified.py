@@ -60,6 +60,8 @@ class UnifiedConfig:
     cg_rtol: float = 0.1
     damping: float = 1.0
     curv_rows: int = 0
+    precond: str = "none"        # UnifiedHF's CG preconditioner: "none" or "grad_sq" (the squared-gradient diagonal)
+    precond_exponent: float = 0.75
     # Validation-monitored training (HIP extension; UnifiedLBFGS and UnifiedSLBFGS). eval_every > 0: the test split
     # is evaluated on the device at iteration 0, every eval_every iterations (epochs for S-LBFGS) and at the end.
     eval_every: int = 0          # 0: off (the unmonitored code path)
@@ -347,13 +349,17 @@ class UnifiedGD(UnifiedOptimizer):
 
 class UnifiedHF(UnifiedOptimizer):
     """Hessian-free (truncated Newton) training (HIP extension, no reference counterpart): engine.hf_solve with the
-    config's max_iters, tolerance, cg_iters, cg_rtol, damping (the initial one) and curv_rows; the loss and l2 are
-    the network's. The damping, reduction-ratio and CG-iteration traces are kept in self.traces."""
+    config's max_iters, tolerance, cg_iters, cg_rtol, damping (the initial one), curv_rows, precond and
+    precond_exponent; the loss and l2 are the network's. The damping, reduction-ratio and CG-iteration traces are
+    kept in self.traces."""
 
     def optimize(self, net, data, config):
         if config.eval_every > 0:
             raise LbfError("UnifiedHF has no resumable form: eval_every > 0 needs UnifiedLBFGS or UnifiedSLBFGS")
+        engine.hf_precond(config.precond, config.precond_exponent)   # an unknown name fails here, before the device
+        precond = None if config.precond == "none" else config.precond   # "none": lbf_hf_solve itself
         hist, info, traces = engine.hf_solve(net.mlp, net.params, data.x, data.y, n_global=data.n_global,
+                                             precond=precond, precond_exponent=config.precond_exponent,
                                              max_iters=config.max_iters, tol=config.tolerance,
                                              cg_iters=config.cg_iters, cg_rtol=config.cg_rtol,
                                              damping0=config.damping, curv_rows=config.curv_rows)
