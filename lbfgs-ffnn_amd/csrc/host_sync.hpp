@@ -3,7 +3,7 @@
 // g++) runs them on the CPU:
 //   RankBarrier - the reusable generation barrier of the in-process rank group (comm.cpp, LocalComm);
 //   TaskFifo    - the S-LBFGS twin's helper thread: tasks run in posting order on one worker thread
-//                 (solvers.cpp, SlbfgsSolver), the poster waits for a task by its ticket.
+//                 (solve_slbfgs.cpp, SlbfgsSolver), the poster waits for a task by its ticket.
 // The reference is single-threaded (src/cuda/common.cuh); neither has a counterpart there.
 #pragma once
 

@@ -87,6 +87,7 @@ private:
 };
 
 inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
+inline long long round4(long long n) { return cdiv(n, 4) * 4; }
 inline int env_int(const char *name, int dflt) {
   const char *e = std::getenv(name);
   return e ? std::atoi(e) : dflt;

@@ -1,13 +1,14 @@
-// Solver drivers: full-batch L-BFGS (CPU/Wolfe and CUDA/Armijo semantics) and S-LBFGS.
+// Solver drivers (solve_*.cpp): full-batch L-BFGS (CPU/Wolfe and CUDA/Armijo semantics), S-LBFGS, GD, SGD,
+// Hessian-free and OWL-QN.
 #pragma once
 
 #include "../../include/lbfgs_amd.h"
 #include "host_sync.hpp"
 #include "runtime.hpp"
 #include "sampler.hpp"
+#include "solver_io.hpp"
 
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <deque>
 #include <exception>
@@ -20,12 +21,13 @@ namespace lbf {
 
 // What the minimizer evaluates: the reference's LossGradFun (src/cuda/minimizer_base.cuh:15-16) plus the
 // dots the line search needs. eval() writes the gradient into g (n+2 floats) and SC_LOSS / SC_TGG /
-// SC_TGP (g.pdir) into the device status block scal, all on ctx()->stream.
+// SC_TGP (g.pdir) into the device status block scal, all on ctx()->stream. tf: null, or the fused optimizer tail
+// (tail.hip) to run behind the evaluation; only a fused_tail() objective is ever handed one (the solver checks).
 struct Objective {
   virtual ~Objective() = default;
   virtual Ctx *ctx() const = 0;
   virtual long long n() const = 0;
-  virtual void eval(const float *x, float *g, const float *pdir, double *scal) = 0;
+  virtual void eval(const float *x, float *g, const float *pdir, double *scal, const TailFuse *tf) = 0;
   virtual long long evals() const = 0;
   virtual long long rows() const { return 0; } // batch rows evaluated (0: not an MLP objective)
   // L2 weight decay inside the objective (loss + 0.5 l2 |x|^2, g + l2 x). When non-zero, the solver announces
@@ -41,14 +43,10 @@ struct Objective {
   // gradient and dots of that same point; together bitwise equal to eval().
   virtual bool split_eval() const { return false; }
   virtual void eval_loss(const float *, double *) {}
-  virtual void eval_grad_after_loss(const float *, float *, const float *, double *) {}
+  virtual void eval_grad_after_loss(const float *, float *, const float *, double *, const TailFuse *) {}
   virtual long long loss_only_evals() const { return 0; }
   virtual long long grad_after_loss_evals() const { return 0; }
-  // Evaluation followed by the fused optimizer tail (tail.hip); only when fused_tail() is true.
-  virtual bool fused_tail() const { return false; }
-  virtual void eval_fused(const float *, float *, const float *, double *, const TailFuse &) {}
-  // eval_grad_after_loss followed by the fused tail (fused_tail() objectives)
-  virtual void eval_grad_after_loss_fused(const float *, float *, const float *, double *, const TailFuse &) {}
+  virtual bool fused_tail() const { return false; } // eval / eval_grad_after_loss can run the fused tail
 };
 
 // The MLP's fused loss+grad over the rank's shard (mean over n_global samples).
@@ -67,8 +65,8 @@ struct MlpObjective : Objective {
   }
   Ctx *ctx() const override { return net->ctx(); }
   long long n() const override { return (long long)net->nparams(); }
-  void eval(const float *x, float *g, const float *pdir, double *scal) override {
-    net->loss_grad(x, g, X, Y, nullptr, nloc, 1.0 / double(nglob), lambda, pdir, scal, nullptr, ww);
+  void eval(const float *x, float *g, const float *pdir, double *scal, const TailFuse *tf) override {
+    net->loss_grad(x, g, X, Y, nullptr, nloc, 1.0 / double(nglob), lambda, pdir, scal, tf, ww);
   }
   long long evals() const override { return net->evals(); }
   long long rows() const override { return net->rows(); }
@@ -79,19 +77,13 @@ struct MlpObjective : Objective {
   void eval_loss(const float *x, double *scal) override {
     net->loss_only(x, X, Y, nullptr, nloc, 1.0 / double(nglob), scal, lambda, ww);
   }
-  void eval_grad_after_loss(const float *x, float *g, const float *pdir, double *scal) override {
-    net->grad_after_loss(x, g, X, nullptr, nloc, 1.0 / double(nglob), lambda, pdir, scal, nullptr, ww);
+  void eval_grad_after_loss(const float *x, float *g, const float *pdir, double *scal,
+                            const TailFuse *tf) override {
+    net->grad_after_loss(x, g, X, nullptr, nloc, 1.0 / double(nglob), lambda, pdir, scal, tf, ww);
   }
   long long loss_only_evals() const override { return net->loss_only_evals(); }
   long long grad_after_loss_evals() const override { return net->grad_after_loss_evals(); }
   bool fused_tail() const override { return true; }
-  void eval_fused(const float *x, float *g, const float *pdir, double *scal, const TailFuse &tf) override {
-    net->loss_grad(x, g, X, Y, nullptr, nloc, 1.0 / double(nglob), lambda, pdir, scal, &tf, ww);
-  }
-  void eval_grad_after_loss_fused(const float *x, float *g, const float *pdir, double *scal,
-                                  const TailFuse &tf) override {
-    net->grad_after_loss(x, g, X, nullptr, nloc, 1.0 / double(nglob), lambda, pdir, scal, &tf, ww);
-  }
 };
 
 // A user callback with the reference's LossGradFun contract: returns the loss, writes the gradient
@@ -111,7 +103,7 @@ struct CallbackObjective : Objective {
   }
   Ctx *ctx() const override { return c; }
   long long n() const override { return nn; }
-  void eval(const float *x, float *g, const float *pdir, double *scal) override;
+  void eval(const float *x, float *g, const float *pdir, double *scal, const TailFuse *) override;
   long long evals() const override { return count; }
 };
 
@@ -128,12 +120,16 @@ public:
   bool converged() const { return converged_; }
 
 private:
-  void eval(const float *x, float *g, const float *pdir); // fused loss+grad, status -> hs_
-  void read_status();
+  // The objective's three evaluations of a point buffer x, its w.w partials announced first; status -> scal().
+  // tf: the fused tail behind the evaluation (fuse_ only)
+  void eval(const float *x, float *g, const float *pdir, const TailFuse *tf = nullptr);
+  void eval_loss(const float *x);
+  void eval_grad_after_loss(const float *x, float *g, const float *pdir, const TailFuse *tf = nullptr);
+  void read_status() { hs_.read(ctx_->stream, hist_.scal()); }
   void writeback();
-  int iterate_wolfe(int iters, lbf_record *rec);
-  int iterate_armijo(int iters, lbf_record *rec);
-  int iterate_spec(int iters, lbf_record *rec);
+  int iterate_wolfe(int iters);
+  int iterate_armijo(int iters);
+  int iterate_spec(int iters);
   bool entry_converged() const;
   // First trial of an iteration (history update, direction, x + alpha p, evaluation), enqueued only.
   // Returns the Armijo trial step (Wolfe takes alpha0 from the device status block). With `ls`, the
@@ -141,12 +137,17 @@ private:
   float begin_iteration(const LsCtlArgs *ls = nullptr);
   // Rest of the iteration once hs_ holds the first trial's status: further trials, role rotation,
   // record.
-  void finish_wolfe(lbf_record *rec, bool spec = false);
+  void finish_wolfe(bool spec = false);
   int grad_fused(double alpha, SpecRecord *r); // finish_wolfe's gradient phase through the fused tail
-  void finish_armijo(float alpha, lbf_record *rec, bool spec = false);
+  void finish_armijo(float alpha, bool spec = false);
   void accept_roles();
-  void mark_prev_accepted(lbf_record *rec, double flag);
-  void record(lbf_record *rec, double loss, double gnorm, double alpha, int trials, int accepted);
+  // The line-search decision's arguments for sequence number seq, and the fused tail request around them
+  // (alphaf: the fp32 trial step; early: the Armijo test in the trial's first backward launch).
+  LsCtlArgs ls_args(int seq, bool first, bool host_fold) const;
+  TailFuse tail_request(const LsCtlArgs &ls, float alphaf, bool early) const;
+  void record(double loss, double gnorm, double alpha, int trials) {
+    rw_.put(loss, gnorm, ms_since(t0_), alpha, trials, -1); // accepted: patched by the next iteration
+  }
 
   // speculative pipeline state
   struct Roles {
@@ -191,13 +192,13 @@ private:
   double *ww_out(const float *x);           // where the producer of x writes (nullptr: no weight decay)
   void announce_ww(const float *x);         // obj_->point_ww for the evaluation of x that follows
   float *x_, *xp_, *xt_, *g_, *gp_, *gt_;
-  PinnedBuf<double> hs_;
+  StatusMirror hs_;
   double loss_ = 0, gg_ = 0;
   float lossf_ = 0;
   int iter_ = 0;
   bool pending_pair_ = false, pending_reset_ = false, converged_ = false;
-  int rec_idx_ = 0;
-  long long evals0_ = 0, rows0_ = 0, lonly0_ = 0, gal0_ = 0; // the objective's counters when this solve began
+  RecordWriter rw_; // begun from rec->size by every iterate()
+  SolveCounters<Objective> cnt_;
   std::chrono::steady_clock::time_point t0_;
 };
 
@@ -248,7 +249,7 @@ private:
   bool started_ = false, have_u_ = false, mu_valid_ = false, next_ready_ = false, converged_ = false;
   EpochDraw cur_, next_;
   int wh_head_ = 0, wh_count_ = 0; // ring of L+1 iterates (w_history)
-  int rec_i_ = 0;
+  RecordWriter rw_;                // begun from rec->size by the first iterate() only
   // Data parallel (a communicator), LBF_SLBFGS_DP_REPLICATED: every rank runs the epoch's whole inner-step
   // chain (identical inputs, identical bits) with no collective; only the full-batch gradient at the
   // anchor (s_lbfgs.hpp:206, 274-284) is sharded, one all-reduce per epoch. LBF_SLBFGS_DP_SLICED: each rank
@@ -289,10 +290,10 @@ private:
   long long ng_ = 0; // floats per gradient in a block (n + 2 loss words, rounded to 4)
   DevBuf<int> idx_;
   PinnedBuf<int> idx_host_; // pinned staging of an epoch's index lists
-  PinnedBuf<double> hs_;
+  StatusMirror hs_;
   int iters_ = 0;
   double last_loss_ = 0, last_gnorm_ = 0;
-  long long evals0_ = 0, rows0_ = 0; // the net's counters when this solve began
+  SolveCounters<Mlp> cnt_; // the side networks below count from zero
   // Twin evaluator: a second workspace of the same network on its own stream, so the two latency-bound
   // minibatch evaluations of a step run concurrently (results unchanged: each is the same launch
   // sequence on its own buffers). Data parallel: the twin's evaluations stop before the all-reduce
@@ -364,6 +365,5 @@ long long owl_penalised_count(const Mlp &net, int l1_bias);
 void fd_hvp_grads(Mlp *net, const float *u, const float *s, const float *X, const float *Y, const int *idx,
                   long long count, double inv_scale, double lambda, double eps, float *wp, float *wm, float *gp,
                   float *gm, double *scal);
-
 
 } // namespace lbf

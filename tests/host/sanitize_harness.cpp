@@ -4,12 +4,15 @@
 //   1. RankBarrier (host_sync.hpp) under the in-process rank group's protocol (comm.cpp LocalComm): every
 //      rank publishes its buffer pointer and count, meets, reads every other rank's, meets again; a rank
 //      that throws breaks the group and the others fail instead of hanging.
-//   2. TaskFifo (host_sync.hpp) under the S-LBFGS twin's protocol (solvers.cpp epoch_steps): tasks posted in
+//   2. TaskFifo (host_sync.hpp) under the S-LBFGS twin's protocol (solve_slbfgs.cpp epoch_steps): tasks posted in
 //      order, the poster waits by ticket before reading what a task produced, an error fails the FIFO for good
 //      (every later task skipped, every later wait rethrows), the destructor runs what is queued.
 //   3. MinibatchSampler (sampler.cpp) against a plain restatement of s_lbfgs.hpp:141-160 (iota(N) per draw).
+//   4. RecordWriter (solver_io.hpp), the solvers' lbf_record rows: rows past the capacity are dropped and never
+//      patched, NULL columns and a NULL record are skipped, a later writer appends.
 #include "host_sync.hpp"
 #include "sampler.hpp"
+#include "solver_io.hpp"
 
 #include <atomic>
 #include <cstdio>
@@ -98,7 +101,7 @@ static void test_rank_group() {
 
 // ---- 2. twin worker ----------------------------------------------------------------------------------
 static void test_task_fifo() {
-  // in-order execution; the poster reads a task's output only after waiting for its ticket (solvers.cpp:
+  // in-order execution; the poster reads a task's output only after waiting for its ticket (solve_slbfgs.cpp:
   // twin_wait(tk[t]) before the context stream waits on the event task t records)
   {
     std::atomic<bool> init_ran{false};
@@ -197,6 +200,77 @@ static void test_sampler() {
     }
 }
 
+// ---- 4. record writer --------------------------------------------------------------------------------
+struct RecArrays { // a record of capacity cap over arrays of cap + 4 sentinel-filled entries
+  static constexpr double kD = -12345.5;
+  static constexpr int kI = -4242;
+  std::vector<double> loss, gnorm, ms, alpha;
+  std::vector<int> trials, accepted;
+  lbf_record rec;
+  explicit RecArrays(int cap)
+      : loss(size_t(cap) + 4, kD), gnorm(loss), ms(loss), alpha(loss), trials(size_t(cap) + 4, kI), accepted(trials),
+        rec{loss.data(), gnorm.data(), ms.data(), alpha.data(), trials.data(), accepted.data(), cap, 0} {}
+  bool untouched_from(int row) const { // rows row.. of every array still hold the sentinel
+    for (size_t i = size_t(row); i < loss.size(); ++i)
+      if (loss[i] != kD || gnorm[i] != kD || ms[i] != kD || alpha[i] != kD || trials[i] != kI || accepted[i] != kI)
+        return false;
+    return true;
+  }
+};
+
+static void test_record_writer() {
+  { // capacity 3, six rows: the first three are kept, nothing past the capacity is written or patched
+    RecArrays a(3);
+    RecordWriter w(&a.rec);
+    for (int k = 0; k < 6; ++k) {
+      w.put(10.0 + k, 20.0 + k, 30.0 + k, 40.0 + k, 50 + k, -1);
+      if (k == 2) {
+        w.patch_prev_accepted(7);
+        CHECK(a.accepted[2] == 7);
+      }
+      if (k == 4) w.patch_prev_accepted(9); // row 4 was dropped: no row to patch
+    }
+    CHECK(a.rec.size == 3);
+    for (int k = 0; k < 3; ++k)
+      CHECK(a.loss[size_t(k)] == 10.0 + k && a.gnorm[size_t(k)] == 20.0 + k && a.ms[size_t(k)] == 30.0 + k &&
+            a.alpha[size_t(k)] == 40.0 + k && a.trials[size_t(k)] == 50 + k);
+    CHECK(a.accepted[0] == -1 && a.accepted[1] == -1 && a.accepted[2] == 7);
+    CHECK(a.untouched_from(3));
+  }
+  { // NULL columns are skipped, the size still advances
+    RecArrays a(3);
+    a.rec.grad_norm = a.rec.time_ms = a.rec.alpha = nullptr;
+    a.rec.ls_trials = a.rec.accepted = nullptr;
+    RecordWriter w(&a.rec);
+    w.put(1.5, 2.5, 3.5, 4.5, 5, 6);
+    w.patch_prev_accepted(1);
+    w.put(1.25, 2.5, 3.5, 4.5, 5, 6);
+    CHECK(a.rec.size == 2 && a.loss[0] == 1.5 && a.loss[1] == 1.25);
+    a.loss[0] = a.loss[1] = RecArrays::kD;
+    CHECK(a.untouched_from(0));
+  }
+  { // no record: every call is a no-op
+    RecordWriter w(nullptr), d;
+    w.put(1.0, 2.0, 3.0, 4.0, 5, 6);
+    w.patch_prev_accepted(1);
+    d.put(1.0, 2.0, 3.0, 4.0, 5, 6);
+    d.patch_prev_accepted(1);
+  }
+  { // a second writer begun on a record that holds two rows appends at row 2
+    RecArrays a(5);
+    RecordWriter first(&a.rec);
+    first.put(1.0, 1.0, 1.0, 1.0, 1, -1);
+    first.put(2.0, 2.0, 2.0, 2.0, 2, -1);
+    CHECK(a.rec.size == 2);
+    RecordWriter second(&a.rec);
+    second.patch_prev_accepted(1); // the last row of the first writer
+    second.put(3.0, 3.0, 3.0, 3.0, 3, -1);
+    CHECK(a.rec.size == 3 && a.loss[0] == 1.0 && a.loss[1] == 2.0 && a.loss[2] == 3.0 && a.trials[2] == 3);
+    CHECK(a.accepted[0] == -1 && a.accepted[1] == 1 && a.accepted[2] == -1);
+    CHECK(a.untouched_from(3));
+  }
+}
+
 // A deliberate unsynchronised write/write pair: the pytest runs it once to prove the sanitizer build is live
 // (ThreadSanitizer must report it).
 static void canary_race() {
@@ -216,6 +290,7 @@ int main(int argc, char **argv) {
   test_rank_group();
   test_task_fifo();
   test_sampler();
+  test_record_writer();
   std::printf("sanitize harness ok\n");
   return 0;
 }

@@ -92,7 +92,7 @@ def _worker(rank, world, port, outdir):
     # (3) communicator id broadcast (the RCCL unique id travels the same way)
     uid = [os.urandom(128) if rank == 0 else None]
     dist.broadcast_object_list(uid, src=0)
-    # (4) S-LBFGS minibatch slicing across ranks (solvers.cpp: [b*r/p, b*(r+1)/p))
+    # (4) S-LBFGS minibatch slicing across ranks (solve_slbfgs.cpp: [b*r/p, b*(r+1)/p))
     idx = O.sample_indices(400, 37, 123, 1)[0]
     mine = idx[37 * rank // world: 37 * (rank + 1) // world]
     np.savez(os.path.join(outdir, f"r{rank}.npz"), l=l, g=g, x=x, losses=losses, uid=np.frombuffer(uid[0], np.uint8),

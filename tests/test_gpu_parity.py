@@ -408,7 +408,7 @@ def _same(h, ref, keys=("loss", "grad_norm", "alpha", "ls_trials", "accepted")):
 
 @pytest.mark.parametrize("line_search", ["wolfe", "armijo"])
 def test_speculative_line_search_is_exact(ctx, pkg, monkeypatch, line_search):
-    """Speculation (ls_ctl + abort flag, solvers.cpp iterate_spec) without the fused tail reproduces
+    """Speculation (ls_ctl + abort flag, solve_lbfgs.cpp iterate_spec) without the fused tail reproduces
     the host-driven loop bit for bit: records, evaluation count, final parameters — across rejections
     of the first trial, convergence inside the speculation window, and split iterate() calls."""
     ref, ref_info, ref_P = _spec_run(pkg, ctx, monkeypatch, 0, line_search, 0.0, 40)

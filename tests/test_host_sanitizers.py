@@ -1,6 +1,7 @@
 """Host-code sanitizer builds: tests/host/sanitize_harness.cpp drives the engine's host
-concurrency (the in-process rank group's RankBarrier, the S-LBFGS twin's TaskFifo; host_sync.hpp) and the
-minibatch sampler (sampler.cpp) on the CPU, compiled with g++ under ThreadSanitizer and under
+concurrency (the in-process rank group's RankBarrier, the S-LBFGS twin's TaskFifo; host_sync.hpp), the
+minibatch sampler (sampler.cpp) and the solvers' record writer (solver_io.hpp) on the CPU, compiled with g++ under
+ThreadSanitizer and under
 AddressSanitizer + UndefinedBehaviorSanitizer. No GPU: the HIP launches are stubbed by host work.
 """
 import os
