@@ -1,5 +1,5 @@
 // Data-parallel communicators of a context (new in this engine: the reference has no collective,
-// SURVEY.md §2.1). The evaluation path (runtime.cpp) only needs one operation: an in-place fp32 sum
+// SURVEY.md §2.1). The evaluation path (mlp_eval.cpp) only needs one operation: an in-place fp32 sum
 // all-reduce on the context stream, once per loss+grad evaluation.
 //
 //   RcclComm   the product route: one process per GPU, ncclAllReduce over xGMI.

@@ -12,7 +12,7 @@
 //   (H v)_l = [A_{l-1} | 1]^T R{dZ_l} + [R{A_{l-1}} | 0]^T dZ_l   (+ lambda v)
 // With the softmax cross-entropy loss (linear last layer, dZ_L = s (p Ysum - y)) only the output step changes:
 //   R{dZ_L} = s Ysum p .* (R{Z_L} - sum_k p_k R{Z_L}_k)                      (rop_out_xent)
-// The products are the engine's MFMA GEMMs (runtime.cpp Mlp::hvp); this file holds the elementwise
+// The products are the engine's MFMA GEMMs (mlp_curvature.cpp Mlp::hvp); this file holds the elementwise
 // R-steps. act' and act'' are taken through the post-activation value a (act.hpp convention):
 // tanh 1-a^2, -2a(1-a^2); sigmoid a(1-a), a(1-a)(1-2a); relu [a>0], 0; linear 1, 0.
 //

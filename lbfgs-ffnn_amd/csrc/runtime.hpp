@@ -1,5 +1,6 @@
-// Host runtime of liblbfgs_amd_abi3.so: context (device, stream, RCCL communicator), the MLP evaluation
-// plan, the device-resident L-BFGS history, and the solver drivers.
+// Host runtime of liblbfgs_amd_abi3.so: context (device, stream, RCCL communicator) and profiler (ctx.cpp), the
+// MLP's plan and layer GEMMs (mlp_plan.cpp), its evaluation routes (mlp_eval.cpp) and curvature products
+// (mlp_curvature.cpp), and the device-resident L-BFGS history (history.cpp). The solver drivers: solvers.hpp.
 #pragma once
 
 #include "internal.hpp"
@@ -239,71 +240,111 @@ public:
   }
 
 private:
-  void forward_phase(const float *P, const float *X, const float *Y, const int *idx, long long B, double inv_scale);
-  void backward_phase(const float *P, float *G, const float *X, const int *idx, long long B, double inv_scale,
-                      double lambda, const float *pdir, double *scal, const TailFuse *tf, bool local,
-                      const float *hilo_in, RedAllArgs *defer = nullptr, WwPart ww = {});
-  struct FwdState {
-    long long B = -1;
-    bool fused = false;
-    int fold = -1, nloss = 0, lstart = 0;
-  } fs_;
-  DevBuf<float> hilo_, words_; // loss-only (hi, lo); data parallel: this rank's [grad | hi | lo] for the collective
-  long long loss_only_ = 0, gal_ = 0;
-  void ensure(long long B);
-  bool side_reduced(int l, bool fused, int nloss) const;
-  GemmDesc fwd_desc(size_t l, const float *P, const float *in, const int *idx, long long B) const;
-  GemmDesc fwd_launch_desc(size_t l, const float *P, const float *in, const int *idx, long long B);
-  void set_asum(GemmDesc &d, size_t l, const float *P, long long B);
+  // ---- layers and plan state (mlp_plan.cpp) ----
   Ctx *ctx_;
   std::vector<Layer> layers_;
   size_t nparams_ = 0;
   int loss_ = LOSS_MSE;
   double l2_ = 0.0;
-  // the output layer on the generic route: loss_diff or loss_xent on A_[nl - 1] -> D_[nl - 1], loss_part_
-  void out_loss(const float *Y, const int *idx, long long B, double inv_scale);
-  long long cap_ = -1, planned_ = -1;
-  std::vector<DevBuf<float>> A_, D_;
-  DevBuf<float> slab_, head_slab_, fslab_, fslab2_;
-  float *fslab_buf(size_t l) const { return (l & 1) ? fslab2_.get() : fslab_.get(); } // forward slabs of layer l
   const bool group_dw_;  // dW of layers 1 and 0 in one launch (Switches::group_dw)
   const bool fold_on_;   // fold into the EPI_HEAD epilogue (Switches::fold; off: the unfolded route, tests)
   const bool show_plan_; // plan() reports each plan on stderr
   bool asum_shown_ = false; // forward() has reported the current plan's A-from-slabs layers
-  bool rowhead_on(long long B) const; // the standalone head fed by the last hidden layer's slabs
+  long long cap_ = -1, planned_ = -1;
+  long long plan_pin_ = -1; // > 0: ensure() plans for this many rows whatever the batch (evaluate's chunks)
   // Planned fold: the last hidden layer's [dW ; db] rows fold_c0_ .. in (fold_ input columns and the
   // bias row) are computed in the forward GEMM's EPI_HEAD epilogue instead of a mostly empty last
   // row tile of its dW GEMM; fold_ = -1: none.
   int fold_ = -1, fold_c0_ = 0;
+  void plan(long long B);
+  void ensure(long long B);
+  bool side_reduced(int l, bool fused) const;
+  bool rowhead_on(long long B) const; // the standalone head fed by the last hidden layer's slabs
   bool gemm_head_on() const; // the output layer runs inside the last hidden layer's forward GEMM
   int dx_tile(long long B, int N) const;
-  DevBuf<double> loss_part_, dots_part_, sse_, colpart_, trows_, tdots_;
+  // the layer GEMMs as the operands and the plan determine them; callers add their destination and route
+  GemmDesc fwd_desc(size_t l, const float *P, const float *in, const int *idx, long long B) const;
+  GemmDesc fwd_launch_desc(size_t l, const float *P, const float *in, const int *idx, long long B);
+  void set_asum(GemmDesc &d, size_t l, const float *P, long long B);
+  GemmDesc dw_desc(int l, const float *in, const int *rows, bool ones, const float *dZ, long long B) const;
+  GemmDesc dx_desc(int l, const float *dZ, const float *Wsrc, int aux_act, float *out, long long B) const;
+  // ---- activation workspace and slabs ----
+  std::vector<DevBuf<float>> A_, D_;
+  DevBuf<float> slab_, head_slab_, fslab_, fslab2_;
+  float *fslab_buf(size_t l) const { return (l & 1) ? fslab2_.get() : fslab_.get(); } // forward slabs of layer l
+  // ---- forward state and the two phases (mlp_eval.cpp) ----
+  struct FwdState {
+    long long B = -1;
+    bool fused = false;
+    int fold = -1, nloss = 0, lstart = 0;
+  } fs_;
+  void forward_phase(const float *P, const float *X, const float *Y, const int *idx, long long B, double inv_scale);
+  // the output layer on the generic route: loss_diff or loss_xent on A_[nl - 1] -> D_[nl - 1], loss_part_
+  void out_loss(const float *Y, const int *idx, long long B, double inv_scale);
+  // What a backward phase writes besides the gradient, and the route it takes after its GEMMs. Default: the
+  // gradient alone, by reduce_all on a single rank, by the reduced route under a communicator or with no rows.
+  struct BwdRoute {
+    const float *pdir = nullptr;    // direction of the g.p dot
+    double *scal = nullptr;         // status block (null: no dots, no finishing launch)
+    const TailFuse *tf = nullptr;   // fused optimizer tail, when every segment reduces in one pass
+    WwPart ww = {};                 // the point's w.w partials
+    bool local = false;             // stop before the all-reduce: [G | hi | lo] left for finish_reduced
+    const float *hilo_in = nullptr; // reduced route: the loss words of the loss-only trial
+    RedAllArgs *defer = nullptr;    // single rank, no status: leave the slabs to the consumer
+  };
+  struct BwdPass { // one backward phase: its arguments, and what it derives from them and from fs_
+    const float *P = nullptr, *X = nullptr;
+    const int *idx = nullptr;
+    long long B = 0;
+    double inv_scale = 0.0, lambda = 0.0;
+    BwdRoute r; // the caller's, with ww cleared when lambda == 0
+    float *G = nullptr, *Gl = nullptr; // Gl: where this rank's gradient lands before the collective
+    bool empty = false, reduced = false, fused = false;
+    int fold = -1, nloss = 0, lstart = -1;
+    long long nfold = 0; // fold rows in the head slab
+  };
+  void backward_phase(const float *P, float *G, const float *X, const int *idx, long long B, double inv_scale,
+                      double lambda, const BwdRoute &route);
+  bool bwd_early(const BwdPass &b, EarlyLs *e) const;
+  GemmDesc bwd_dw_desc(const BwdPass &b, int l) const;
+  void bwd_launch(const BwdPass &b, const EarlyLs *early);
+  void bwd_segments(const BwdPass &b, RedAllArgs &ra) const;
+  void bwd_words(const BwdPass &b, const RedAllArgs &ra);
+  void bwd_tail(const BwdPass &b, RedAllArgs &ra);
+  void bwd_finish_reduced(const BwdPass &b, const RedAllArgs &ra);
+  // ---- reduction and tail buffers ----
+  DevBuf<float> hilo_, words_; // loss-only (hi, lo); data parallel: this rank's [grad | hi | lo] for the collective
+  DevBuf<double> loss_part_, dots_part_, colpart_, trows_, tdots_;
   DevBuf<unsigned> cols_done_; // tail_cols arrival counter (zero between launches)
-  // R-pass workspace (hvp, gnvp): R{Z}, R{A}, R{dZ} and delta per layer, two products, one segment
+  // ---- R-pass workspace (mlp_curvature.cpp): R{Z}, R{A}, R{dZ} and delta per layer, two products, one segment ----
   std::vector<DevBuf<float>> RZ_, RA_, RD_, DL_;
   DevBuf<float> T1_, T2_, seg_;
   DevBuf<float> gsq_slab_; // grad_sq: the row chunks' partial slabs of one layer
   long long rcap_ = -1;
   void rpass_ensure(long long B); // grows the workspace to B rows
-  // gnvp in two steps. gn_prepare: the workspaces and the unfused forward pass of the batch. gn_apply: the
-  // R-forward, the loss's Hessian, the backward pass, the all-reduce and + lambda V, on the activations
-  // gn_prepare left. The prepared state holds until the next call that writes the activation workspace (forward,
-  // loss_grad, loss_only, evaluate, hvp, gnvp, grad_sq); P, X, Y, idx and B must be gn_prepare's.
-  void gn_prepare(const float *P, const float *X, const float *Y, const int *idx, long long B);
-  void gn_apply(const float *P, const float *V, const float *X, const float *Y, const int *idx, long long B,
-                double inv_scale, double lambda, float *Gv);
-  // gn_cg's state: r, p, Ap, the partial tables [pap | rr x 2 | xdots x 3 | rz x 2], the status block, the abort word
-  DevBuf<float> cg_r_, cg_p_, cg_ap_;
-  DevBuf<double> cg_part_, cg_st_;
-  DevBuf<int> cg_abort_;
-  PinnedBuf<double> cg_hst_;
   // the R-pass products of layer l on B rows, with the forward, dW and dX plans of ensure(B)
   void rpass_linear_fwd(long long B, int l, const float *Wsrc, const float *in, const int *rows, bool with_bias,
                         float *out);
   void rpass_weight_grad(long long B, int l, const float *in, const int *rows, bool ones, const float *dZ,
                          float *dst);
   void rpass_back_prod(long long B, int l, const float *dZ, const float *Wsrc, int aux_act, float *out);
-  // evaluate(): per-workgroup loss partials and counts [rows, correct, topk] of every chunk, the confusion cells,
+  void curv_finish(float *out, double lambda, const float *V, const int *abort); // all-reduce, + lambda V
+  void curv_empty(float *out, double lambda, const float *V, const int *abort);  // an empty share: zeros that join
+  // gnvp in two steps. gn_prepare: the workspaces and the unfused forward pass of the batch. gn_apply: the
+  // R-forward, the loss's Hessian, the backward pass, the all-reduce and + lambda V, on the activations
+  // gn_prepare left. The prepared state holds until the next call that writes the activation workspace (forward,
+  // loss_grad, loss_only, evaluate, hvp, gnvp, grad_sq); P, X, idx and B must be gn_prepare's.
+  void gn_prepare(const float *P, const float *X, const int *idx, long long B);
+  void gn_apply(const float *P, const float *V, const float *X, const float *Y, const int *idx, long long B,
+                double inv_scale, double lambda, float *Gv);
+  // ---- CG state (gn_cg) ----
+  // r, p, Ap, the partial tables [pap | rr x 2 | xdots x 3 | rz x 2], the status block, the abort word
+  DevBuf<float> cg_r_, cg_p_, cg_ap_;
+  DevBuf<double> cg_part_, cg_st_;
+  DevBuf<int> cg_abort_;
+  PinnedBuf<double> cg_hst_;
+  // ---- evaluate buffers ----
+  // per-workgroup loss partials and counts [rows, correct, topk] of every chunk, the confusion cells,
   // the partials' sum, the all-reduce words
   DevBuf<double> ev_part_, ev_sum_;
   DevBuf<unsigned> ev_cpart_;
@@ -311,9 +352,8 @@ private:
   DevBuf<float> ev_words_;
   PinnedBuf<float> ev_hwords_;
   PinnedBuf<double> ev_hsum_;
-  long long plan_pin_ = -1; // > 0: ensure() plans for this many rows whatever the batch (evaluate's chunks)
-  long long evals_ = 0, rows_ = 0;
-  void plan(long long B);
+  // ---- counters ----
+  long long evals_ = 0, rows_ = 0, loss_only_ = 0, gal_ = 0;
 };
 
 // Device-resident history of (s, y) pairs and its fp64 Gram state.
@@ -360,11 +400,6 @@ private:
   DevBuf<double> gdots_;
   DevBuf<unsigned> gcount_;
   bool gfin_on_ = false;
-};
-
-struct LbfgsRecordRow {
-  double loss, gnorm, time_ms, alpha;
-  int trials, accepted;
 };
 
 } // namespace lbf

@@ -1,4 +1,4 @@
-"""Reads the LBF_SHOW_PLAN=1 report (stderr, runtime.cpp Mlp::plan and Mlp::forward) so that a test can assert the
+"""Reads the LBF_SHOW_PLAN=1 report (stderr, mlp_plan.cpp plan, mlp_eval.cpp forward) so that a test can assert the
 tile and split plan its shape was chosen for. The switch is read when the Mlp is constructed: set it with
 monkeypatch.setenv before, and pass capfd.readouterr().err here after the first call on the network."""
 import re

@@ -2,7 +2,7 @@
 contiguous sample shards, one all-reduce of [grad | loss] per evaluation scaled by 1/N_global, the
 optimizer state replicated on every rank (identical inputs -> identical trajectories), the S-LBFGS
 minibatch slicing, and the communicator-id broadcast. The per-rank evaluations use the oracle (the
-CPU restatement); the GPU ranks run the same decomposition with RCCL (lbfgs-ffnn_amd/csrc/runtime.cpp).
+CPU restatement); the GPU ranks run the same decomposition with RCCL (lbfgs-ffnn_amd/csrc/mlp_eval.cpp).
 """
 import os
 import sys

@@ -1,7 +1,7 @@
 """The data-parallel evaluation path on ONE GPU, through a 1-rank RCCL communicator.
 
 `lbf_comm_init(ctx, 1, 0, id)` creates a real RCCL communicator, and every evaluation then takes the
-multi-rank route of runtime.cpp (per-rank reduce -> fp32 (hi, lo) loss words -> ncclAllReduce over
+multi-rank route of mlp_eval.cpp (per-rank reduce -> fp32 (hi, lo) loss words -> ncclAllReduce over
 [grad | hi | lo] -> tail / finalize over the reduced buffer) — the code the driver's 2/4/8-GPU bench
 runs, minus the cross-GPU hop. A 1-rank all-reduce is the identity, so the results must equal the
 single-GPU path: gradients bit for bit, losses to the (hi, lo) split's 2^-48, and whole L-BFGS /
@@ -55,7 +55,7 @@ def test_dp_loss_grad_equals_single(ctx, dp_ctx, pkg, dims, acts, N):
 
 @pytest.mark.parametrize("line_search", ["wolfe", "armijo"])
 def test_dp_lbfgs_trajectory_equals_single(ctx, dp_ctx, pkg, line_search):
-    """Speculative L-BFGS with the fused tail over the all-reduced buffer (runtime.cpp DP branch)."""
+    """Speculative L-BFGS with the fused tail over the all-reduced buffer (mlp_eval.cpp bwd_tail)."""
     dims, acts = [784, 64, 10], ["relu", "linear"]
     Xh, Yh = pkg.synth_mnist(2048)
     out = []

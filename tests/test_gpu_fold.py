@@ -1,4 +1,4 @@
-"""The EPI_HEAD fold (runtime.cpp Mlp::plan, head_core.hpp tile<.., FOLD>): the last hidden layer's
+"""The EPI_HEAD fold (mlp_plan.cpp Mlp::plan, head_core.hpp tile<.., FOLD>): the last hidden layer's
 [dW ; db] rows past the dW GEMM's last full row tile (<= 16 input columns + the bias row) are
 accumulated in the forward GEMM's epilogue instead of a mostly empty dW row tile.
 

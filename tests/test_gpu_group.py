@@ -1,4 +1,4 @@
-"""The grouped weight-gradient launch (gemm.hip gemm_group, runtime.cpp Mlp::backward_phase).
+"""The grouped weight-gradient launch (gemm.hip gemm_group, mlp_eval.cpp Mlp::bwd_launch).
 
 Small batches (S-LBFGS minibatches, b = 256) run the dW GEMMs of layers 1 and 0 as one launch whose
 z-planes hold both problems' split-K grids. Each split still sums its own k range in the same order and

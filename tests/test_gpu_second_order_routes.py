@@ -1,4 +1,4 @@
-"""Mlp.hvp and Mlp.gnvp against torch fp64 on every GEMM route the R-pass takes (runtime.cpp rpass_linear_fwd,
+"""Mlp.hvp and Mlp.gnvp against torch fp64 on every GEMM route the R-pass takes (mlp_curvature.cpp rpass_linear_fwd,
 rpass_weight_grad, rpass_back_prod, the unfused forward() with its A-from-slabs prologue; hvp.hip's row loops).
 
 Each case names the plan it was chosen for: per layer the forward tile and splits, the dW tile, splits and k chunk,
