@@ -22,18 +22,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import __graft_entry__  # noqa: E402
+from gpu_helpers import dev, shard  # noqa: E402 (tests/ is this script's directory, and the parent's path)
 
 CFG2 = ([784, 128, 10], ["relu", "linear"], 60000)
 SLB = ([784, 16, 10], ["relu", "linear"], 512)
 SLB_ARGS = dict(M=5, L=4, b=32, b_H=16, step=0.02, max_epochs=2, tol=0.0, lam=1e-4)
-
-
-def shard(N, world, r):
-    return N * r // world, N * (r + 1) // world
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
 
 
 def allreduce_input(rank):

@@ -8,7 +8,7 @@ import torch
 
 import exact_nets as en
 import test_gpu_exact as ge
-from test_gpu_gn import gn_ref, hess_ref
+from ref_mlp import gn_ref, hess_ref
 
 CASES = ge.all_cases()
 

@@ -16,6 +16,9 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import dev, host
+from ref_mlp import MSE, hess_ref, objective, rel
+
 pytestmark = pytest.mark.gpu
 
 LOSS_RTOL = 1e-5
@@ -24,20 +27,6 @@ DIR_RTOL = 1e-5
 HVP_RTOL = 1e-4
 PAD = 8
 SENTINEL = 0x7FC5A5A5   # a quiet NaN: a sentinel that is read poisons the result
-ACTF = {"linear": lambda z: z, "relu": torch.relu, "tanh": torch.tanh, "sigmoid": torch.sigmoid}
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def host(t):
-    return t.double().cpu().numpy()
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 
 
 def raw(pkg):
@@ -83,19 +72,6 @@ def random_problem(dims, N, seed=0):
     Y = np.zeros((N, dims[-1]))
     Y[np.arange(N), rng.integers(0, dims[-1], N)] = 1.0
     return X, Y
-
-
-def torch_obj(dims, acts, X, Y, inv_scale, lam):
-    def f(P):
-        a, off = X, 0
-        for l in range(len(acts)):
-            i, o = dims[l], dims[l + 1]
-            W = P[off:off + i * o].reshape(i, o)
-            b = P[off + i * o:off + (i + 1) * o]
-            off += (i + 1) * o
-            a = ACTF[acts[l]](a @ W + b)
-        return 0.5 * inv_scale * ((a - Y) ** 2).sum() + 0.5 * lam * (P * P).sum()
-    return f
 
 
 # ------------------------------------------------------------------------------------------------
@@ -224,8 +200,8 @@ def test_hvp_unaligned(ctx, pkg, O, dims, acts, N, offs, lam, gather):
     vv, hv = view(vh, offs[3]), out_view(vh.shape, offs[0])
     net.hvp(Pv, vv, Xv, Yv, idx=idx, inv_scale=1.0 / B, l2=lam, out=hv)
     check_guard(hv, vv, Pv, Xv, Yv)
-    f = torch_obj(dims, acts, torch.from_numpy(r["X"][rows]), torch.from_numpy(r["Y"][rows]), 1.0 / B, lam)
-    _, ref = torch.autograd.functional.hvp(f, r["P"].double().cpu(), torch.from_numpy(vh).double())
+    ref = hess_ref(dims, acts, MSE, r["P"].double().cpu(), torch.from_numpy(vh).double(),
+                   torch.from_numpy(r["X"][rows]), torch.from_numpy(r["Y"][rows]), 1.0 / B, lam)
     aligned = net.hvp(r["P"], dev(vh), dev(r["X"]), dev(r["Y"]), idx=idx, inv_scale=1.0 / B, l2=lam)
     err = rel(host(hv), ref.numpy())
     print(f"{dims} lam={lam} gather={gather}: hvp rel {err:.2e}; vs aligned {rel(host(hv), host(aligned)):.2e}")
@@ -243,7 +219,7 @@ def test_fd_hvp_unaligned(ctx, pkg, O, dims, acts, N, offs):
     vv, yv = view(vh, offs[3]), out_view(vh.shape, offs[0])
     net.fd_hvp(Pv, vv, Xv, Yv, inv_scale=1.0 / N, l2=lam, eps=eps, out=yv)
     check_guard(yv, vv, Pv, Xv, Yv)
-    f = torch_obj(dims, acts, torch.from_numpy(r["X"]), torch.from_numpy(r["Y"]), 1.0 / N, lam)
+    f = objective(dims, acts, MSE, torch.from_numpy(r["X"]), torch.from_numpy(r["Y"]), 1.0 / N, lam)
     Ph, v64 = r["P"].double().cpu(), torch.from_numpy(vh).double()
     g = [torch.autograd.grad(f(p), p)[0] for p in ((Ph + eps * v64).requires_grad_(True),
                                                    (Ph - eps * v64).requires_grad_(True))]

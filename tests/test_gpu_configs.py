@@ -14,24 +14,13 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import dev, host
 from plan_report import T128, lost_route, on_plan_device, planned_layers
+from ref_mlp import rel
 
 pytestmark = pytest.mark.gpu
 
 CFG5 = ([4096, 2048, 1024, 1], ["relu", "relu", "linear"])
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def host(t):
-    return t.double().cpu().numpy()
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 
 
 def test_cfg3_lbfgs_m20_trajectory(ctx, pkg, O):

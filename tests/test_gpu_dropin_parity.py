@@ -30,14 +30,14 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_xent import LOSS_RTOL, torch_obj  # 1e-5: check_loss_grad there, test_loss_grad_matches_oracle in test_gpu_parity.py
+from ref_mlp import XENT, bias_mask, net_out, nparams, objective
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "lbfgs-ffnn_amd", "build", "parity_hip")
+LOSS_RTOL = 1e-5      # test_gpu_xent.py::check_loss_grad, test_loss_grad_matches_oracle in test_gpu_parity.py
 GAP = 1e-4            # test_gpu_eval.py::check_against_oracle: gap >= 1e-4 max(1, |out|max) is clear of the fp32 forward
-XENT = "softmax_xent"
 SLBFGS_LAMBDA = 1e-4  # lbf_slbfgs_params.lambda, which the header leaves at the library's default
 
 
@@ -56,7 +56,7 @@ class Problem:
         Y[np.arange(n), np.argmax(X.astype(np.float64) @ teacher, 1)] = 1.0  # one-hot, learnable
         self.X = {"train": X[:n_train], "test": X[n_train:]}
         self.Y = {"train": Y[:n_train], "test": Y[n_train:]}
-        self.nparams = sum((dims[i] + 1) * dims[i + 1] for i in range(len(acts)))
+        self.nparams = nparams(dims)
 
     def write(self, d):
         for split in ("train", "test"):
@@ -64,12 +64,7 @@ class Problem:
             self.Y[split].tofile(os.path.join(d, f"{self.tag}_Y_{split}.f32"))
 
     def weights_mask(self):
-        m, off = np.zeros(self.nparams, bool), 0
-        for i in range(len(self.acts)):
-            w = self.dims[i] * self.dims[i + 1]
-            m[off:off + w] = True
-            off += w + self.dims[i + 1]
-        return m
+        return ~bias_mask(self.dims)
 
 
 def problems():
@@ -144,7 +139,7 @@ def t64(a):
 def objective64(prob, P, split="train", l2=0.0, l1=0.0, l1_bias=False):
     """data loss (a mean over the rows) + 0.5 l2 |w|^2 + l1 |w|_1 over the penalised coordinates (lbfgs_amd.h)."""
     X, Y = prob.X[split], prob.Y[split]
-    f = torch_obj(prob.dims, prob.acts, t64(X), t64(Y), 1.0 / len(X), l2, prob.loss)
+    f = objective(prob.dims, prob.acts, prob.loss, t64(X), t64(Y), 1.0 / len(X), l2)
     v = float(f(t64(P)))
     if l1:
         w = np.asarray(P, np.float64)
@@ -153,13 +148,7 @@ def objective64(prob, P, split="train", l2=0.0, l1=0.0, l1_bias=False):
 
 
 def forward64(prob, P, X):
-    act = {"linear": lambda z: z, "relu": lambda z: np.maximum(z, 0.0), "tanh": np.tanh}
-    a, off, P = np.asarray(X, np.float64), 0, np.asarray(P, np.float64)
-    for l, name in enumerate(prob.acts):
-        i, o = prob.dims[l], prob.dims[l + 1]
-        a = act[name](a @ P[off:off + i * o].reshape(i, o) + P[off + i * o:off + (i + 1) * o])
-        off += (i + 1) * o
-    return a
+    return net_out(prob.dims, prob.acts, t64(X))(t64(P)).numpy()
 
 
 def clear_rows(z):

@@ -6,11 +6,12 @@ rule (unified_launcher.hpp:154-199: the lowest index wins a tie, a NaN never win
 the loss and the predictions against the fp64 oracle; then chunking, the in-process rank group, the isolation from
 an open solver, and the validation loop of UnifiedLauncher.train.
 """
-import threading
-
 import numpy as np
 import pytest
 import torch
+
+from gpu_helpers import dev, run_ranks
+from ref_mlp import one_hot
 
 pytestmark = pytest.mark.gpu
 
@@ -27,16 +28,6 @@ NETS = [
 ]
 CASES = [(d, a, l) for d, a, ls in NETS for l in ls]
 CASE_IDS = ["-".join(map(str, d)) + "-" + l for d, a, l in CASES]
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def one_hot(rng, N, Out):
-    Y = np.zeros((N, Out), np.float32)
-    Y[np.arange(N), rng.integers(0, Out, N)] = 1.0
-    return Y
 
 
 def soft(rng, N, Out):
@@ -286,33 +277,6 @@ def test_chunking_changes_nothing_but_the_sum_order(ctx, pkg, dims, acts, loss):
     a, b = net.evaluate(P, X, Y, idx=idx, pred=True, chunk=0), net.evaluate(P, X, Y, idx=idx, pred=True, chunk=64)
     assert (a.correct, a.rows) == (b.correct, b.rows) and torch.equal(a.pred, b.pred)
     assert abs(a.loss - b.loss) <= 200 * Out * 2.0 ** -53 * abs(a.loss)
-
-
-def run_ranks(pkg, world, body, timeout=240):
-    """body(rank, ctx) on `world` threads, each rank of one in-process group on GPU 0 (as tests/test_gpu_ranks.py)."""
-    ctxs = [pkg.Context(0, use_torch_stream=False) for _ in range(world)]
-    pkg.Context.comm_init_local(ctxs)
-    torch.cuda.synchronize()
-    out, err = [None] * world, [None] * world
-
-    def th(r):
-        try:
-            torch.cuda.set_device(0)
-            out[r] = body(r, ctxs[r])
-            torch.cuda.synchronize()
-        except BaseException as e:  # noqa: BLE001 (re-raised below)
-            err[r] = e
-
-    ts = [threading.Thread(target=th, args=(r,), daemon=True) for r in range(world)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join(timeout)
-    assert not any(t.is_alive() for t in ts), "a rank thread did not finish"
-    for e in err:
-        if e is not None:
-            raise e
-    return out
 
 
 @pytest.mark.parametrize("world,N", [(2, 1001), (3, 1001), (3, 2)], ids=["w2-1001", "w3-1001", "w3-2-empty-share"])

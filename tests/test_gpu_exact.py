@@ -18,11 +18,11 @@ import pytest
 import torch
 
 import exact_nets as en
+from gpu_helpers import run_ranks
 from plan_report import T32x128, T64x128, T128, lost_route, on_plan_device, planned_asum, planned_layers
 from test_gpu_gemm_pipe import B_RAGGED
 from test_gpu_parity import NETS as PARITY_NETS
 from test_gpu_pcg import GS
-from test_gpu_ranks import run_ranks
 from test_gpu_second_order_routes import CASES as ROUTE_CASES
 
 pytestmark = pytest.mark.gpu

@@ -17,6 +17,9 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import dev, host
+from ref_mlp import rel
+
 pytestmark = pytest.mark.gpu
 
 N_FULL = 60000
@@ -26,19 +29,6 @@ CFG4 = ([784, 512, 256, 10], ["relu", "relu", "linear"])
 # the reference's only deep GPU workload: tests/fashion-mnist/main_gpu_deep.cpp:14-17 (784-256-128-64-10,
 # ReLU x 3, Linear; L-BFGS m = 100 and m = 10 on N = 60000, :78, :92; CUDA route and init)
 DEEP = ([784, 256, 128, 64, 10], ["relu", "relu", "relu", "linear"])
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def host(t):
-    return t.double().cpu().numpy()
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 
 
 @pytest.fixture(scope="module")

@@ -5,19 +5,12 @@ parity target; tolerance 1e-3 relative on the recorded losses (fp32 evaluation o
 identical iteration counts where a stopping rule fires."""
 import numpy as np
 import pytest
-import torch
+
+from gpu_helpers import dev, host
 
 pytestmark = pytest.mark.gpu
 
 DIMS, ACTS = [784, 32, 10], ["relu", "linear"]
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def host(t):
-    return t.double().cpu().numpy()
 
 
 @pytest.mark.parametrize("momentum", [0.9, 0.0])

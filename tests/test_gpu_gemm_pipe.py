@@ -19,38 +19,15 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import dev
 from plan_report import T32x128, T128, lost_route, on_plan_device, planned_layers
+from ref_mlp import XENT, loss_grad, rel
 
 pytestmark = pytest.mark.gpu
 
 LOSS_RTOL = 1e-5
 GRAD_RTOL = 1e-4
-XENT = "softmax_xent"
-ACTF = {"linear": lambda z: z, "relu": torch.relu, "tanh": torch.tanh, "sigmoid": torch.sigmoid}
 B_RAGGED = 32900
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
-
-
-def xent_ref(dims, acts, P, X, Y):
-    """Mean softmax cross-entropy of the net's logits and its gradient, fp64 (torch autograd)."""
-    p = torch.from_numpy(np.asarray(P, np.float64)).requires_grad_(True)
-    a, off = torch.from_numpy(X.astype(np.float64)), 0
-    for l in range(len(acts)):
-        i, o = dims[l], dims[l + 1]
-        a = ACTF[acts[l]](a @ p[off:off + i * o].reshape(i, o) + p[off + i * o:off + (i + 1) * o])
-        off += (i + 1) * o
-    Yt = torch.from_numpy(Y.astype(np.float64))
-    loss = (Yt * (torch.logsumexp(a, 1, keepdim=True) - a)).sum() / X.shape[0]
-    (g,) = torch.autograd.grad(loss, p)
-    return float(loss.detach()), g.numpy()
 
 
 def run_case(ctx, pkg, O, monkeypatch, capfd, dims, acts, loss, N, rows=None):
@@ -67,7 +44,7 @@ def run_case(ctx, pkg, O, monkeypatch, capfd, dims, acts, loss, N, rows=None):
     Ph = P.double().cpu().numpy()
     if loss == XENT:
         sel = slice(None) if rows is None else rows
-        l_ref, g_ref = xent_ref(dims, acts, Ph, Xh[sel], Yh[sel])
+        l_ref, g_ref = loss_grad(dims, acts, XENT, Ph, Xh[sel], Yh[sel], 1.0 / B)
     else:
         l_ref, g_ref = O.Net(dims, acts).loss_grad(Ph, Xh.astype(np.float64), Yh.astype(np.float64), idx=rows)
     dl, dg = abs(val - l_ref) / abs(l_ref), rel(g.double().cpu().numpy(), g_ref)

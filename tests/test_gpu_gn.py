@@ -13,12 +13,13 @@ G = H, 1e-5 against the engine's own exact product (both from the same fp32 prod
 import numpy as np
 import pytest
 import torch
-from torch.func import jvp, vjp
+
+from gpu_helpers import dev
+from ref_mlp import XENT, gap, gn_ref, hess_ref, one_hot, rel
 
 pytestmark = pytest.mark.gpu
 
 GN_RTOL = 1e-4
-XENT = "softmax_xent"
 NETS = [
     ([20, 16, 3], ["tanh", "linear"]),
     ([30, 24, 12, 4], ["sigmoid", "relu", "linear"]),
@@ -30,59 +31,6 @@ NETS = [
 ]
 # linear last layer and Out >= 2: those of NETS, and test_gpu_xent.py's fifth (an output wider than 16)
 XENT_NETS = [(d, a) for d, a in NETS if a[-1] == "linear" and d[-1] >= 2] + [([784, 300, 20], ["relu", "linear"])]
-ACTS = {"linear": lambda z: z, "relu": torch.relu, "tanh": torch.tanh, "sigmoid": torch.sigmoid}
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def relerr(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).norm() / b.norm())
-
-
-def net_out(dims, acts, X):
-    def f(P):
-        a, off = X, 0
-        for l in range(len(acts)):
-            i, o = dims[l], dims[l + 1]
-            W = P[off:off + i * o].reshape(i, o)
-            b = P[off + i * o:off + (i + 1) * o]
-            off += (i + 1) * o
-            a = ACTS[acts[l]](a @ W + b)
-        return a
-    return f
-
-
-def gn_ref(dims, acts, loss, P, v, X, Y, inv_scale, lam):
-    """G(P) v + lam v in the dtype of the arguments (fp64 on the CPU)."""
-    f = net_out(dims, acts, X)
-    out, Jv = jvp(f, (P,), (v,))
-    if loss == XENT:
-        p = torch.softmax(out, 1)
-        HJv = inv_scale * Y.sum(1, keepdim=True) * p * (Jv - (p * Jv).sum(1, keepdim=True))
-    else:
-        HJv = inv_scale * Jv
-    _, pull = vjp(f, P)
-    return pull(HJv)[0] + lam * v
-
-
-def hess_ref(dims, acts, loss, P, v, X, Y, inv_scale, lam):
-    """H(P) v + lam v by double backward, as test_gpu_hvp.py / test_gpu_xent.py."""
-    f = net_out(dims, acts, X)
-
-    def obj(P):
-        a = f(P)
-        data = (Y * (torch.logsumexp(a, 1, keepdim=True) - a)).sum() if loss == XENT else 0.5 * ((a - Y) ** 2).sum()
-        return inv_scale * data + 0.5 * lam * (P * P).sum()
-    return torch.autograd.functional.hvp(obj, P, v)[1]
-
-
-def one_hot(rng, N, Out):
-    Y = np.zeros((N, Out), np.float32)
-    Y[np.arange(N), rng.integers(0, Out, N)] = 1.0
-    return Y
 
 
 def case_data(pkg, dims, acts, loss, gather, N=37):
@@ -107,10 +55,6 @@ def references(dims, acts, loss, P, X, Y, v, rows, lam):
             hess_ref(dims, acts, loss, a[0], a[1], a[2], a[3], 1.0 / B, lam))
 
 
-def gap(G, H):
-    return float((G - H).norm() / H.norm())
-
-
 CASES = [("mse", d, a) for d, a in NETS] + [(XENT, d, a) for d, a in XENT_NETS]
 
 
@@ -124,7 +68,7 @@ def test_gnvp_matches_torch_fp64(ctx, pkg, loss, dims, acts, lam, gather):
     net = pkg.Mlp(ctx, dims, acts, loss=loss)
     idx = torch.from_numpy(rows.astype(np.int32)).cuda() if gather else None
     gv = net.gnvp(dev(P), dev(v), dev(X), dev(Y), idx=idx, inv_scale=1.0 / len(rows), l2=lam)
-    err = relerr(gv, G)
+    err = rel(gv, G)
     print(f"gnvp {loss} {dims} lam={lam} gather={gather}: rel {err:.2e}, |G-H|/|H| {gap(G, H):.2f}")
     assert err <= GN_RTOL
 
@@ -143,7 +87,7 @@ def test_gnvp_wide_split_k_route(ctx, pkg, loss):
                   l2=1e-4)
     a = [t.double() for t in (P.cpu(), torch.from_numpy(v), torch.from_numpy(Xh[rows]), torch.from_numpy(Yh[rows]))]
     ref = gn_ref(dims, acts, loss, a[0], a[1], a[2], a[3], 1.0 / 128, 1e-4)
-    err = relerr(gv, ref)
+    err = rel(gv, ref)
     print(f"gnvp wide {loss}: rel {err:.2e}")
     assert err <= GN_RTOL
 
@@ -170,7 +114,7 @@ def test_gnvp_equals_hvp_where_g_is_h(ctx, pkg, loss, dims, acts, zero_residual)
     v = dev(rng.standard_normal(net.nparams))
     hv = net.hvp(P, v, X, Y, l2=1e-4).clone()
     gv = net.gnvp(P, v, X, Y, l2=1e-4)
-    err = relerr(gv, hv)
+    err = rel(gv, hv)
     print(f"gnvp vs hvp {loss} {dims} zero_residual={zero_residual}: rel {err:.2e}")
     assert err <= 1e-5
 
@@ -286,7 +230,7 @@ def test_gnvp_unaligned_pointers(ctx, pkg):
     Pv.copy_(P)
     vv.copy_(v)
     net.gnvp(Pv, vv, X, Y, l2=1e-4, out=ov)
-    err = relerr(ov, aligned)
+    err = rel(ov, aligned)
     print(f"gnvp unaligned vs aligned: rel {err:.2e}, bitwise {torch.equal(ov, aligned)}")
     assert torch.equal(ov, aligned)
     assert float(bufs[2][0]) == 7.0 and bool((bufs[2][1 + n:] == 7.0).all())  # nothing stored outside the view
@@ -321,7 +265,7 @@ def test_slbfgs_pair_is_the_gauss_newton_product(ctx, pkg, mnist512):
     for e in events[1:]:
         u, s = rec[e, 1].contiguous(), (rec[e, 1] - rec[e - 1, 1]).contiguous()
         ref = net2.gnvp(u, s, X, Y, inv_scale=1.0 / 512, l2=1e-4)
-        err = relerr(rec[e, 2], ref)
+        err = rel(rec[e, 2], ref)
         print(f"event {e}: recorded y vs gnvp rel {err:.2e}")
         assert err <= 1e-5
         assert not bool(rec[e, 3].any())

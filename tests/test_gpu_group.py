@@ -9,11 +9,9 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import dev
+
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
 
 
 CASES = [([784, 512, 256, 10], ["relu", "relu", "linear"], 256),   # config 4's minibatch

@@ -1,10 +1,10 @@
 """Hessian-free optimisation: the device-side Gauss-Newton conjugate gradients (Mlp.gn_cg /
 lbf_mlp_gn_cg, lbfgs-ffnn_amd/csrc/cg.hip) and the solver built on them (engine.hf_solve / lbf_hf_solve).
 
-The reference is torch fp64 on the CPU, restated here: the Gauss-Newton product as in test_gpu_gn.py (jvp of the
-network output, the loss's Hessian in closed form, vjp back), textbook CG from x = 0 on it, and the outer
-iteration of lbfgs_amd.h (Armijo backtracking from alpha = 1, Levenberg-Marquardt damping from the first trial's
-reduction ratio). The same code run in fp32 on the CPU gives the error an fp32 implementation is allowed.
+The reference is torch fp64 on the CPU (ref_mlp.py): the Gauss-Newton product (jvp of the network output, the
+loss's Hessian in closed form, vjp back), textbook CG from x = 0 on it, and the outer iteration of lbfgs_amd.h
+(Armijo backtracking from alpha = 1, Levenberg-Marquardt damping from the first trial's reduction ratio). The
+same code run in fp32 on the CPU gives the error an fp32 implementation is allowed.
 
 Bounds. Few-step CG iterates: max(1e-4, 3 x the CPU fp32 restatement's error), the project's gradient rule.
 Converged CG and the least-squares known answer: 1e-4 (condition numbers <= 25, the fp32 restatement is below
@@ -12,202 +12,19 @@ Converged CG and the least-squares known answer: 1e-4 (condition numbers <= 25, 
 bound); the reference's reduction ratios are first shown to stay 5e-3 away from both thresholds, so an fp32
 evaluation cannot flip a damping decision.
 """
-import threading
-
 import numpy as np
 import pytest
 import torch
-from torch.func import jacrev, jvp, vjp
+
+from gpu_helpers import dev, gpu_args, make_net, run_ranks, solver_inputs
+from ref_mlp import NETS, SMALL, XENT, gn_matrix, gn_ref, hf_ref, host_args, make_case, nparams, pcg_ref, rel
 
 pytestmark = pytest.mark.gpu
 
-XENT = "softmax_xent"
-ACTS = {"linear": lambda z: z, "relu": torch.relu, "tanh": torch.tanh, "sigmoid": torch.sigmoid}
-# name: dims, acts, loss, rows (N), gathered rows (0: all)
-NETS = {
-    "n387": ([20, 16, 3], ["tanh", "linear"], "mse", 37, 0),            # n % 4 != 0, n < one sweep workgroup
-    "xent4": ([30, 24, 12, 4], ["sigmoid", "relu", "linear"], XENT, 37, 0),
-    "xent10": ([64, 32, 10], ["relu", "linear"], XENT, 257, 0),
-    "mnist": ([784, 128, 10], ["relu", "linear"], XENT, 257, 0),
-    "wide": ([784, 512, 256, 10], ["tanh", "tanh", "linear"], "mse", 1000, 64),  # n = 535818: 524 workgroups
-}
-SMALL = ["n387", "xent4", "xent10"]
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def relerr(a, b):
-    a, b = torch.as_tensor(a).double().cpu(), torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm())
-
-
-def one_hot(rng, N, Out):
-    Y = np.zeros((N, Out), np.float32)
-    Y[np.arange(N), rng.integers(0, Out, N)] = 1.0
-    return Y
-
-
-def nparams(dims):
-    return sum((dims[i] + 1) * dims[i + 1] for i in range(len(dims) - 1))
-
-
-def make_case(pkg, name, loss=None, seed=0):
-    """Host inputs of a case: dict(dims, acts, loss, P, X, Y, rows, b). The start point is the engine's seed-123
-    CPU-stream init; b is a random right-hand side."""
-    dims, acts, dloss, N, gathered = NETS[name]
-    loss = loss or dloss
-    rng = np.random.default_rng(1000 * seed + len(dims) * 7 + dims[0])
-    if dims[0] == 784:
-        X, Y = pkg.synth_mnist(N)
-    else:
-        X = rng.standard_normal((N, dims[0])).astype(np.float32)
-        Y = one_hot(rng, N, dims[-1]) if loss == XENT else rng.standard_normal((N, dims[-1])).astype(np.float32)
-    P = pkg.init_params_host(dims, acts, 123, "cpu")
-    rows = rng.permutation(N)[:gathered] if gathered else np.arange(N)
-    b = rng.standard_normal(P.size).astype(np.float32)
-    return dict(name=name, dims=dims, acts=acts, loss=loss, P=P, X=X, Y=Y, rows=rows, b=b)
-
-
-def gpu_args(c):
-    """(P, b, X, Y, idx) on the device."""
-    gathered = len(c["rows"]) != len(c["X"])
-    idx = torch.from_numpy(c["rows"].astype(np.int32)).cuda() if gathered else None
-    return dev(c["P"]), dev(c["b"]), dev(c["X"]), dev(c["Y"]), idx
-
-
-def host_args(c, dtype):
-    """(P, b, X, Y) of the batch rows as CPU tensors of dtype."""
-    r = c["rows"]
-    return tuple(torch.from_numpy(np.asarray(t)).to(dtype) for t in (c["P"], c["b"], c["X"][r], c["Y"][r]))
-
-
-# ---------------------------------------------------------------- the reference (any dtype, CPU)
-def net_out(dims, acts, X):
-    def f(P):
-        a, off = X, 0
-        for l in range(len(acts)):
-            i, o = dims[l], dims[l + 1]
-            W = P[off:off + i * o].reshape(i, o)
-            bias = P[off + i * o:off + (i + 1) * o]
-            off += (i + 1) * o
-            a = ACTS[acts[l]](a @ W + bias)
-        return a
-    return f
-
-
-def gn_ref(dims, acts, loss, P, v, X, Y, inv_scale, lam):
-    """G(P) v + lam v (test_gpu_gn.py's gn_ref)."""
-    f = net_out(dims, acts, X)
-    out, Jv = jvp(f, (P,), (v,))
-    if loss == XENT:
-        p = torch.softmax(out, 1)
-        HJv = inv_scale * Y.sum(1, keepdim=True) * p * (Jv - (p * Jv).sum(1, keepdim=True))
-    else:
-        HJv = inv_scale * Jv
-    _, pull = vjp(f, P)
-    return pull(HJv)[0] + lam * v
-
-
-def gn_matrix(dims, acts, loss, P, X, Y, inv_scale):
-    """The explicit Gauss-Newton matrix from the network's Jacobian (small nets only)."""
-    f = net_out(dims, acts, X)
-    J = jacrev(f)(P)  # [B, Out, n]
-    if loss == XENT:
-        p = torch.softmax(f(P), 1)[:, :, None]
-        HJ = inv_scale * Y.sum(1)[:, None, None] * p * (J - (p * J).sum(1, keepdim=True))
-    else:
-        HJ = inv_scale * J
-    return torch.einsum("bon,bom->nm", J, HJ)
-
-
-def objective(dims, acts, loss, X, Y, inv_scale, l2):
-    f = net_out(dims, acts, X)
-
-    def obj(P):
-        a = f(P)
-        data = (Y * (torch.logsumexp(a, 1, keepdim=True) - a)).sum() if loss == XENT else 0.5 * ((a - Y) ** 2).sum()
-        return inv_scale * data + 0.5 * l2 * (P * P).sum()
-    return obj
-
-
-def cg_ref(A, b, max_iters, rtol):
-    """CG from x = 0 with the engine's stopping rule; returns (x, r, iterations, status)."""
-    x, r, p = torch.zeros_like(b), b.clone(), b.clone()
-    rr0 = rr = float(r @ r)
-    if rr0 == 0.0:
-        return x, r, 0, 0
-    for k in range(max_iters):
-        Ap = A(p)
-        pAp = float(p @ Ap)
-        if not (pAp > 0.0) or not np.isfinite(pAp):
-            return x, r, k, 2
-        alpha = rr / pAp
-        x = x + alpha * p
-        r = r - alpha * Ap
-        rrn = float(r @ r)
-        if rrn <= rtol * rtol * rr0:
-            return x, r, k + 1, 0
-        p = r + (rrn / rr) * p
-        rr = rrn
-    return x, r, max_iters, 1
-
-
-def hf_ref(c, dtype, l2, iters, damping0=1.0, cg_iters=10, cg_rtol=0.1, c1=1e-4, rho=0.5, max_line_iters=20,
-           up=1.5, down=2.0 / 3.0, lo=0.25, hi=0.75):
-    """lbf_hf_solve's outer iteration (lbfgs_amd.h) in `dtype` on the CPU."""
-    P, _, X, Y = host_args(c, dtype)
-    dims, acts, loss = c["dims"], c["acts"], c["loss"]
-    inv = 1.0 / X.shape[0]
-    obj = objective(dims, acts, loss, X, Y, inv, l2)
-    lam = damping0
-    out = dict(loss=[], cg=[], trials=[], accepted=[], alpha=[], damping=[], ratio=[])
-    for _ in range(iters):
-        Pg = P.clone().requires_grad_(True)
-        fv = obj(Pg)
-        g, = torch.autograd.grad(fv, Pg)
-        f = float(fv.detach())
-        b = -g
-        x, r, k, _ = cg_ref(lambda v: gn_ref(dims, acts, loss, P, v, X, Y, inv, l2 + lam), b, cg_iters, cg_rtol)
-        q = -0.5 * float(x @ (b + r)) - 0.5 * lam * float(x @ x)
-        gp = float(g @ x)
-        alpha, trials, accepted, f1 = 1.0, 0, 0, f
-        for t in range(max_line_iters):
-            ft = float(obj(P + alpha * x))
-            if t == 0:
-                f1 = ft
-            trials += 1
-            if ft <= f + c1 * alpha * gp:
-                accepted = 1
-                break
-            alpha *= rho
-        if accepted:
-            P = P + alpha * x
-        ratio = (f1 - f) / q
-        if ratio < lo:
-            lam *= up
-        elif ratio > hi:
-            lam *= down
-        for key, val in zip(("loss", "cg", "trials", "accepted", "alpha", "damping", "ratio"),
-                            (f, k, trials, accepted, alpha if accepted else 0.0, lam, ratio)):
-            out[key].append(val)
-    out["P"] = P
-    return out
-
-
-def make_net(pkg, ctx, c, l2=0.0):
-    return pkg.Mlp(ctx, c["dims"], c["acts"], loss=c["loss"], l2=l2)
-
-
-_cases = {}
-
 
 def case(pkg, name, loss=None, seed=0):
-    key = (name, loss, seed)
-    if key not in _cases:
-        _cases[key] = make_case(pkg, name, loss, seed)
-    return _cases[key]
+    """`wide` regresses on synth_mnist's one-hot labels here."""
+    return make_case(pkg, NETS, name, loss, seed, keep_labels=True)
 
 
 def run_cg(pkg, ctx, c, net=None, **kw):
@@ -225,10 +42,10 @@ def test_cg_five_steps_match_fp64(ctx, pkg, name, damping):
     for dt in (torch.float64, torch.float32):
         P, b, X, Y = host_args(c, dt)
         A = lambda v: gn_ref(c["dims"], c["acts"], c["loss"], P, v, X, Y, 1.0 / X.shape[0], damping)  # noqa: E731
-        ref[dt] = cg_ref(A, b, 5, 0.0)[0]
-    own = relerr(ref[torch.float32], ref[torch.float64])
+        ref[dt] = pcg_ref(A, b, None, 5, 0.0)[0]
+    own = rel(ref[torch.float32], ref[torch.float64])
     x, info = run_cg(pkg, ctx, c, damping=damping, max_iters=5, rtol=0.0)
-    err = relerr(x, ref[torch.float64])
+    err = rel(x, ref[torch.float64])
     print(f"cg k=5 {name} damping={damping}: rel {err:.2e}, cpu fp32 {own:.2e}")
     assert info["iterations"] == 5 and info["status"] == 1
     assert err <= max(1e-4, 3 * own)
@@ -242,7 +59,7 @@ def test_cg_converged_matches_dense_solve(ctx, pkg, name):
     A = G + 0.1 * np.eye(G.shape[0])
     want = np.linalg.solve(A, b.numpy())
     x, info = run_cg(pkg, ctx, c, damping=0.1, max_iters=40, rtol=0.0)
-    err = relerr(x, want)
+    err = rel(x, want)
     print(f"cg converged {name}: rel {err:.2e}, cond {np.linalg.cond(A):.1f}, iterations {info['iterations']}")
     assert err <= 1e-4
 
@@ -261,7 +78,7 @@ def test_cg_least_squares_known_answer(ctx, pkg):
     A1 = np.hstack([X.astype(np.float64), np.ones((N, 1))])
     W = np.linalg.lstsq(A1, Y.astype(np.float64), rcond=None)[0]  # [41, 8]: weights then the bias row
     want = np.concatenate([W[:40].ravel(), W[40]])
-    err = relerr(Pd + x, want)
+    err = rel(Pd + x, want)
     print(f"least squares: rel {err:.2e}, iterations {info['iterations']}")
     assert err <= 1e-4
 
@@ -342,7 +159,7 @@ def test_cg_unaligned_pointers(ctx, pkg, name):
     keep = [t.clone() for t in bufs[:2]]
     x, info = make_net(pkg, ctx, c).gn_cg(Pu, bu, X, Y, idx=idx, damping=0.1, max_iters=6, rtol=0.0, out=xu)
     assert x.data_ptr() == xu.data_ptr()
-    err = relerr(x, want)
+    err = rel(x, want)
     print(f"unaligned {name}: rel {err:.2e}")
     assert err <= 1e-6
     assert torch.equal(bufs[0], keep[0]) and torch.equal(bufs[1], keep[1])
@@ -361,7 +178,7 @@ def test_cg_first_iteration_is_the_gauss_newton_product(ctx, pkg, name):
     alpha = float(bd @ bd) / float(bd @ Ab)
     assert abs(info["rr0"] - float(bd @ bd)) <= 1e-12 * info["rr0"]
     assert abs(info["xb"] / info["rr0"] - alpha) <= 1e-6 * alpha
-    assert relerr(x, alpha * bd) <= 1e-6
+    assert rel(x, alpha * bd) <= 1e-6
     rr = float((bd - alpha * Ab).norm() ** 2)
     assert abs(info["rr"] - rr) <= 1e-5 * rr
 
@@ -369,11 +186,6 @@ def test_cg_first_iteration_is_the_gauss_newton_product(ctx, pkg, name):
 # ---------------------------------------------------------------- the solver
 TRAJ = [(n, l, l2) for n in SMALL for l in ("mse", XENT) for l2 in (0.0, 1e-3)]
 TRAJ_SEED = 2  # every reduction ratio of the fp64 reference >= 8e-3 from 0.25 and 0.75 on all twelve cases
-
-
-def solver_inputs(c):
-    """All rows of the case, no gather: (P, X, Y) on the device (P a fresh copy: the solver updates it)."""
-    return dev(c["P"]), dev(c["X"][c["rows"]]), dev(c["Y"][c["rows"]])
 
 
 @pytest.mark.parametrize("name,loss,l2", TRAJ, ids=[f"{n}-{l}-{l2}" for n, l, l2 in TRAJ])
@@ -386,7 +198,7 @@ def test_hf_trajectory_matches_fp64(ctx, pkg, name, loss, l2):
     P, X, Y = solver_inputs(c)
     hist, info, tr = pkg.hf_solve(net, P, X, Y, max_iters=8, tol=0.0, damping0=1.0, cg_iters=10, cg_rtol=0.1)
     dl = float(np.abs(hist["loss"] - np.array(ref["loss"])).max())
-    dp = relerr(P, ref["P"])
+    dp = rel(P, ref["P"])
     print(f"hf {name} {loss} l2={l2}: loss dev {dl:.2e}, params rel {dp:.2e}, ratio margin {margin:.3f}, "
           f"cg {list(tr['cg'])}, trials {list(hist['ls_trials'])}")
     assert info.iterations == 8
@@ -473,33 +285,6 @@ def test_hf_curv_rows_needs_a_single_rank(pkg):
 
 
 # ---------------------------------------------------------------- two ranks
-def run_ranks(pkg, world, body, timeout=240):
-    """body(rank, ctx) on `world` threads, each rank of one in-process group on GPU 0 (test_gpu_ranks.py's)."""
-    ctxs = [pkg.Context(0, use_torch_stream=False) for _ in range(world)]
-    pkg.Context.comm_init_local(ctxs)
-    torch.cuda.synchronize()
-    out, err = [None] * world, [None] * world
-
-    def th(r):
-        try:
-            torch.cuda.set_device(0)
-            out[r] = body(r, ctxs[r])
-            torch.cuda.synchronize()
-        except BaseException as e:  # noqa: BLE001 (re-raised below)
-            err[r] = e
-
-    ts = [threading.Thread(target=th, args=(r,), daemon=True) for r in range(world)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join(timeout)
-    assert not any(t.is_alive() for t in ts), "a rank thread did not finish"
-    for e in err:
-        if e is not None:
-            raise e
-    return out
-
-
 @pytest.mark.parametrize("split", [100, 0], ids=["unequal", "empty-shard"])
 def test_world2_cg(ctx, pkg, split):
     """Shards [0, split) and [split, N): both ranks bitwise equal, the single rank's answer, and an early stop
@@ -528,7 +313,7 @@ def test_world2_cg(ctx, pkg, split):
         assert bool(torch.isfinite(xa).all())
         assert torch.equal(xa, out[0][0][0]) and ia == out[0][0][1]  # against rank 0
     assert out[0][0][1]["iterations"] == oi["iterations"] < 50
-    err = relerr(out[0][0][0], one)
+    err = rel(out[0][0][0], one)
     print(f"world 2 cg (split {split}): against one rank rel {err:.2e}")
     assert err <= 1e-5
 

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from ref_mlp import MSE, hess_ref
+
 pytestmark = pytest.mark.gpu
 
 NETS = [
@@ -21,20 +23,6 @@ NETS = [
     ([4, 6, 12], ["tanh", "linear"]),
     ([10, 5, 20], ["relu", "sigmoid"]),
 ]
-ACTS = {"linear": lambda z: z, "relu": torch.relu, "tanh": torch.tanh, "sigmoid": torch.sigmoid}
-
-
-def torch_loss(dims, acts, X, Y, inv_scale, lam):
-    def f(P):
-        a, off = X, 0
-        for l in range(len(acts)):
-            i, o = dims[l], dims[l + 1]
-            W = P[off:off + i * o].reshape(i, o)
-            b = P[off + i * o:off + (i + 1) * o]
-            off += (i + 1) * o
-            a = ACTS[acts[l]](a @ W + b)
-        return 0.5 * inv_scale * ((a - Y) ** 2).sum() + 0.5 * lam * (P * P).sum()
-    return f
 
 
 @pytest.mark.parametrize("dims,acts", NETS)
@@ -55,8 +43,8 @@ def test_hvp_matches_torch_fp64(ctx, pkg, dims, acts, lam, gather):
     B = len(rows)
     Xd, Yd = torch.from_numpy(X).cuda(), torch.from_numpy(Y).cuda()
     hv = net.hvp(P, v, Xd, Yd, idx=idx, inv_scale=1.0 / B, l2=lam)
-    f = torch_loss(dims, acts, torch.from_numpy(X[rows]).double(), torch.from_numpy(Y[rows]).double(), 1.0 / B, lam)
-    _, ref = torch.autograd.functional.hvp(f, P.double().cpu(), v.double().cpu())
+    ref = hess_ref(dims, acts, MSE, P.double().cpu(), v.double().cpu(), torch.from_numpy(X[rows]).double(),
+                   torch.from_numpy(Y[rows]).double(), 1.0 / B, lam)
     err = (hv.double().cpu() - ref).norm() / ref.norm()
     assert err <= 1e-4, float(err)
 

@@ -3,7 +3,7 @@ minimise and report
 
     data loss + 0.5 * l2 * ||w||^2,        gradient: data gradient + l2 * w,
 
-against torch fp64 autograd of that objective, written here (torch_obj). Both losses, three nets:
+against torch fp64 autograd of that objective (ref_mlp.objective). Both losses, three nets:
   [784,32,10] relu/linear, N = 256      the fused-head route
   [37,50,3] tanh/linear, N = 100        the generic route; n = 2053 parameters: every w.w partial kernel has a
                                         ragged last block (2053 is no multiple of 64 or 256)
@@ -23,11 +23,12 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_xent import dev, host, rel, run_ranks, shard, torch_obj
+import ref_mlp
+from gpu_helpers import dev, host, run_ranks, shard
+from ref_mlp import MSE, XENT, rel
 
 pytestmark = pytest.mark.gpu
 
-XENT, MSE = "softmax_xent", "mse"
 NETS = {
     "mnist32": ([784, 32, 10], ["relu", "linear"], 256),
     "tanh50": ([37, 50, 3], ["tanh", "linear"], 100),
@@ -42,13 +43,12 @@ def data_of(pkg, case):
         return pkg.synth_mnist(N)
     rng = np.random.default_rng(1)
     X = rng.standard_normal((N, dims[0])).astype(np.float32)
-    Y = np.zeros((N, dims[-1]), np.float32)
-    Y[np.arange(N), rng.integers(0, dims[-1], N)] = 1.0
-    return X, Y
+    return X, ref_mlp.one_hot(rng, N, dims[-1])
 
 
 def objective(dims, acts, Xh, Yh, lam, loss):
-    return torch_obj(dims, acts, torch.from_numpy(Xh).double(), torch.from_numpy(Yh).double(), 1.0 / len(Xh), lam, loss)
+    return ref_mlp.objective(dims, acts, loss, torch.from_numpy(Xh).double(), torch.from_numpy(Yh).double(),
+                             1.0 / len(Xh), lam)
 
 
 def value_grad(f, P):
@@ -343,7 +343,7 @@ def test_gd_and_sgd(ctx, pkg, loss):
         assert abs(info.final_grad_norm - float(f_end[1].norm())) <= 1e-4 * float(f_end[1].norm())
 
         def make_f(lo, hi, l2=l2):
-            return torch_obj(dims, acts, Xt[lo:hi], Yt[lo:hi], 1.0 / (hi - lo), l2, loss)
+            return ref_mlp.objective(dims, acts, loss, Xt[lo:hi], Yt[lo:hi], 1.0 / (hi - lo), l2)
 
         P = P0.clone()
         hist, _ = pkg.sgd_solve(net, P, X, Y, batch=32, lr=0.05, momentum=0.9, max_epochs=3, tol=0.0)

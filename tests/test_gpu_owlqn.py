@@ -13,88 +13,22 @@ equality and every pair's y.s ten times above the storing threshold, so an fp32 
 LASSO: 1e-4 against fp64 coordinate descent (the fp64 restatement reaches 5.9e-9, the fp32 one 5.8e-6).
 """
 import ctypes as C
-import threading
 
 import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import dev, make_net, run_ranks, solver_inputs
+from ref_mlp import NETS, SMALL, XENT, bias_mask, make_case, nparams, objective, rel
+
 pytestmark = pytest.mark.gpu
 
-XENT = "softmax_xent"
-ACTS = {"linear": lambda z: z, "relu": torch.relu, "tanh": torch.tanh, "sigmoid": torch.sigmoid}
-# name: dims, acts, loss, rows (N)
-NETS = {
-    "n387": ([20, 16, 3], ["tanh", "linear"], "mse", 37),              # n % 4 != 0, two sweep workgroups
-    "xent4": ([30, 24, 12, 4], ["sigmoid", "relu", "linear"], XENT, 37),
-    "xent10": ([64, 32, 10], ["relu", "linear"], XENT, 257),
-    "mnist": ([784, 128, 10], ["relu", "linear"], XENT, 257),
-    "wide": ([784, 512, 256, 10], ["tanh", "tanh", "linear"], "mse", 64),  # n = 535818: 2094 sweep workgroups
-}
-SMALL = ["n387", "xent4", "xent10"]
 F32 = np.float32
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def relerr(a, b):
-    a, b = torch.as_tensor(a).double().cpu(), torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm())
-
-
-def one_hot(rng, N, Out):
-    Y = np.zeros((N, Out), np.float32)
-    Y[np.arange(N), rng.integers(0, Out, N)] = 1.0
-    return Y
-
-
-def nparams(dims):
-    return sum((dims[i] + 1) * dims[i + 1] for i in range(len(dims) - 1))
-
-
-def bias_mask(dims):
-    """True on the bias coordinates of the flat parameters: each layer is [W (in x out) | b (out)]."""
-    m, off = np.zeros(nparams(dims), bool), 0
-    for i in range(len(dims) - 1):
-        m[off + dims[i] * dims[i + 1]:off + (dims[i] + 1) * dims[i + 1]] = True
-        off += (dims[i] + 1) * dims[i + 1]
-    return m
-
-
-def make_case(pkg, name, loss=None, seed=0):
-    """Host inputs of a case: dict(dims, acts, loss, P, X, Y). The start point is the engine's seed-123 CPU-stream
-    init."""
-    dims, acts, dloss, N = NETS[name]
-    loss = loss or dloss
-    rng = np.random.default_rng(1000 * seed + len(dims) * 7 + dims[0])
-    if dims[0] == 784:
-        X, Y = pkg.synth_mnist(N)
-    else:
-        X = rng.standard_normal((N, dims[0])).astype(np.float32)
-        Y = one_hot(rng, N, dims[-1]) if loss == XENT else rng.standard_normal((N, dims[-1])).astype(np.float32)
-    P = pkg.init_params_host(dims, acts, 123, "cpu")
-    return dict(name=name, dims=dims, acts=acts, loss=loss, P=P, X=X, Y=Y)
-
-
-_cases = {}
-
-
 def case(pkg, name, loss=None, seed=0):
-    key = (name, loss, seed)
-    if key not in _cases:
-        _cases[key] = make_case(pkg, name, loss, seed)
-    return _cases[key]
-
-
-def make_net(pkg, ctx, c, l2=0.0):
-    return pkg.Mlp(ctx, c["dims"], c["acts"], loss=c["loss"], l2=l2)
-
-
-def solver_inputs(c):
-    """(P, X, Y) on the device (P a fresh copy: the solver updates it)."""
-    return dev(c["P"]), dev(c["X"]), dev(c["Y"])
+    """The sweeps read only the shapes of `wide`; the solver cases are the ungathered ones."""
+    return make_case(pkg, NETS, name, loss, seed)
 
 
 # ---------------------------------------------------------------- the sweeps in numpy fp32
@@ -236,29 +170,6 @@ def test_trial_ww_is_the_point_s_own(ctx, pkg):
 
 
 # ---------------------------------------------------------------- the reference (any dtype, CPU)
-def net_out(dims, acts, X):
-    def f(P):
-        a, off = X, 0
-        for l in range(len(acts)):
-            i, o = dims[l], dims[l + 1]
-            W = P[off:off + i * o].reshape(i, o)
-            bias = P[off + i * o:off + (i + 1) * o]
-            off += (i + 1) * o
-            a = ACTS[acts[l]](a @ W + bias)
-        return a
-    return f
-
-
-def objective(dims, acts, loss, X, Y, inv_scale, l2):
-    f = net_out(dims, acts, X)
-
-    def obj(P):
-        a = f(P)
-        data = (Y * (torch.logsumexp(a, 1, keepdim=True) - a)).sum() if loss == XENT else 0.5 * ((a - Y) ** 2).sum()
-        return inv_scale * data + 0.5 * l2 * (P * P).sum()
-    return obj
-
-
 def owlqn_ref(c, dtype, l1, l2, iters, m=10, l1_bias=False, c1=1e-4, rho=0.5, max_line_iters=20, tol=0.0):
     """lbf_owlqn_solve's iteration (lbfgs_amd.h) in `dtype` on the CPU. Also returns the smallest Armijo slack
     |F(x+) - (F + c1 dec)| / |F| over all trials and the smallest y.s over all pairs."""
@@ -358,13 +269,13 @@ def test_owlqn_trajectory_matches_fp64(ctx, pkg, name, loss, l1, l2):
     assert ref["ys"] >= 1e-9, ref["ys"]
     r32 = owlqn_ref(c, torch.float32, l1, l2, TRAJ_ITERS)
     own_f = float(np.abs(np.array(r32["loss"]) - np.array(ref["loss"])).max()) if len(r32["loss"]) == TRAJ_ITERS else 0.0
-    own_p = relerr(r32["P"], ref["P"])
+    own_p = rel(r32["P"], ref["P"])
     own_z = int(((r32["P"] == 0) != (ref["P"] == 0)).sum())
     net = make_net(pkg, ctx, c, l2=l2)
     P, X, Y = solver_inputs(c)
     hist, info, stats = pkg.owlqn_solve(net, P, X, Y, max_iters=TRAJ_ITERS, tol=0.0, m=10, l1=l1)
     df = float(np.abs(hist["loss"] - np.array(ref["loss"])).max())
-    dp = relerr(P, ref["P"])
+    dp = rel(P, ref["P"])
     dz = int(((P.cpu() == 0) != (ref["P"] == 0)).sum())
     print(f"owlqn {name} {loss} l1={l1} l2={l2}: F dev {df:.2e} (cpu fp32 {own_f:.2e}), params rel {dp:.2e} "
           f"({own_p:.2e}), pattern {dz} ({own_z}), zeros {stats['zeros']}/{stats['penalised']}, "
@@ -385,7 +296,7 @@ def test_owlqn_without_history(ctx, pkg):
     P, X, Y = solver_inputs(c)
     hist, info, _ = pkg.owlqn_solve(make_net(pkg, ctx, c), P, X, Y, max_iters=6, tol=0.0, m=0, l1=1e-2)
     assert list(hist["ls_trials"]) == ref["trials"] and list(hist["accepted"]) == ref["accepted"]
-    assert float(np.abs(hist["loss"] - np.array(ref["loss"])).max()) <= 1e-3 and relerr(P, ref["P"]) <= 1e-3
+    assert float(np.abs(hist["loss"] - np.array(ref["loss"])).max()) <= 1e-3 and rel(P, ref["P"]) <= 1e-3
 
 
 # ---------------------------------------------------------------- LASSO known answer
@@ -413,7 +324,8 @@ def test_owlqn_lasso_known_answer(ctx, pkg):
     X = rng.standard_normal((N, 40)).astype(np.float32)
     Y = rng.standard_normal((N, 8)).astype(np.float32)
     want = lasso_cd(X.astype(np.float64), Y.astype(np.float64), l1)
-    c = dict(dims=dims, acts=acts, loss="mse", P=pkg.init_params_host(dims, acts, 123, "cpu"), X=X, Y=Y)
+    c = dict(dims=dims, acts=acts, loss="mse", P=pkg.init_params_host(dims, acts, 123, "cpu"), X=X, Y=Y,
+             rows=np.arange(N))
     r64 = owlqn_ref(c, torch.float64, l1, 0.0, 20)
     r32 = owlqn_ref(c, torch.float32, l1, 0.0, 20)
     e64, e32 = float(np.abs(r64["P"].numpy() - want).max()), float(np.abs(r32["P"].double().numpy() - want).max())
@@ -484,33 +396,6 @@ def test_owlqn_invalid_parameters(ctx, pkg):
 
 
 # ---------------------------------------------------------------- two ranks
-def run_ranks(pkg, world, body, timeout=240):
-    """body(rank, ctx) on `world` threads, each rank of one in-process group on GPU 0 (test_gpu_ranks.py's)."""
-    ctxs = [pkg.Context(0, use_torch_stream=False) for _ in range(world)]
-    pkg.Context.comm_init_local(ctxs)
-    torch.cuda.synchronize()
-    out, err = [None] * world, [None] * world
-
-    def th(r):
-        try:
-            torch.cuda.set_device(0)
-            out[r] = body(r, ctxs[r])
-            torch.cuda.synchronize()
-        except BaseException as e:  # noqa: BLE001 (re-raised below)
-            err[r] = e
-
-    ts = [threading.Thread(target=th, args=(r,), daemon=True) for r in range(world)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join(timeout)
-    assert not any(t.is_alive() for t in ts), "a rank thread did not finish"
-    for e in err:
-        if e is not None:
-            raise e
-    return out
-
-
 @pytest.mark.parametrize("split", [100, 0], ids=["unequal", "empty-shard"])
 def test_world2_owlqn(ctx, pkg, split):
     c = case(pkg, "xent10")
@@ -536,7 +421,7 @@ def test_world2_owlqn(ctx, pkg, split):
         assert np.array_equal(out[0][1][k], h1[k]), k
     # the first step is min(1, 1 / |pg|) of a gradient summed over the shards in another order: equal to rounding
     np.testing.assert_allclose(out[0][1]["alpha"], h1["alpha"], rtol=1e-5, atol=0)
-    err = relerr(out[0][0], P)
+    err = rel(out[0][0], P)
     print(f"world 2 owlqn (split {split}): params against one rank rel {err:.2e}")
     assert err <= 1e-5
 

@@ -8,26 +8,15 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import dev, host
 from plan_report import T32x128, T64x128, lost_route, on_plan_device, planned_layers
+from ref_mlp import rel
 
 pytestmark = pytest.mark.gpu
 
 LOSS_RTOL = 1e-5
 GRAD_RTOL = 1e-4
 DIR_RTOL = 1e-5
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def host(t):
-    return t.double().cpu().numpy()
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 
 
 def random_problem(dims, N, seed=0, onehot=True):

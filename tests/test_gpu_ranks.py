@@ -14,57 +14,14 @@ The reference has no collective; the split rests on the loss bein
 per-call rel <= 1e-5"): the shard sums are added in another order than one GPU's split-K slabs, so
 results agree to fp32 rounding, not bitwise; ranks of one group agree bitwise with each other.
 """
-import threading
-
 import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import dev, host, run_ranks, shard
+from ref_mlp import rel
+
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def host(t):
-    return t.double().cpu().numpy()
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
-
-
-def run_ranks(pkg, world, body, timeout=240):
-    """body(rank, ctx) on `world` threads, each rank of one in-process group on GPU 0."""
-    ctxs = [pkg.Context(0, use_torch_stream=False) for _ in range(world)]
-    pkg.Context.comm_init_local(ctxs)
-    torch.cuda.synchronize()
-    out, err = [None] * world, [None] * world
-
-    def th(r):
-        try:
-            torch.cuda.set_device(0)
-            out[r] = body(r, ctxs[r])
-            torch.cuda.synchronize()
-        except BaseException as e:  # noqa: BLE001 (re-raised below)
-            err[r] = e
-
-    ts = [threading.Thread(target=th, args=(r,), daemon=True) for r in range(world)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join(timeout)
-    assert not any(t.is_alive() for t in ts), "a rank thread did not finish"
-    for e in err:
-        if e is not None:
-            raise e
-    return out
-
-
-def shard(N, world, r):
-    return N * r // world, N * (r + 1) // world
 
 
 def test_local_group_allreduce(pkg):

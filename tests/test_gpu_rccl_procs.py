@@ -28,7 +28,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
 import rccl_worker  # noqa: E402
-from test_gpu_ranks import run_ranks  # noqa: E402
+from gpu_helpers import run_ranks  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

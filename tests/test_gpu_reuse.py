@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import dev
+
 pytestmark = pytest.mark.gpu
 
 NETS = [
@@ -20,10 +22,6 @@ NETS = [
     ([784, 512, 256, 10], ["relu", "relu", "linear"]),
 ]
 ROWS = 2048
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
 
 
 def steps(X, Y, v, idx, empty):

@@ -7,7 +7,7 @@ built with LBF_SHOW_PLAN=1 and the report on stderr must equal that plan, else t
 route (Mlp::plan replayed for 256 CUs; on a device with another CU count only the numbers are checked).
 
 Inputs: X ~ N(0,1) in fp32, squared-error targets N(0,1), cross-entropy targets unnormalised non-negative rows
-(Ysum varies), the engine's seed-123 CPU-stream init, v ~ N(0,1), inv_scale = 1/B. References: test_gpu_gn.py's
+(Ysum varies), the engine's seed-123 CPU-stream init, v ~ N(0,1), inv_scale = 1/B. References: ref_mlp.py's
 gn_ref (jvp, closed-form H_L, vjp) and hess_ref (double backward), fp64 on the CPU on the selected rows.
 
 Bounds: ||got - ref|| <= 1e-4 ||ref|| over the whole vector (the project's HVP / GN bound) and, over every
@@ -25,8 +25,9 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import dev
 from plan_report import T32x128, T64x64, T64x128, T128, lost_route, on_plan_device, planned_asum, planned_layers
-from test_gpu_gn import XENT, dev, gap, gn_ref, hess_ref
+from ref_mlp import XENT, gap, gn_ref, hess_ref, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -119,10 +120,6 @@ def segments(dims):
         out += [(f"W{l}", off, off + w), (f"b{l}", off + w, off + w + dims[l + 1])]
         off += w + dims[l + 1]
     return out
-
-
-def rel(a, b):
-    return float((a.double() - b).norm() / b.norm())
 
 
 SEGMENT_WORST = {"gpu": 0.0, "fp32": 0.0}

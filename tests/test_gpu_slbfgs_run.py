@@ -7,15 +7,9 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import dev, host
+
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def host(t):
-    return t.double().cpu().numpy()
 
 
 DIMS, ACTS = [784, 64, 10], ["relu", "linear"]

@@ -13,67 +13,25 @@ Routes (Mlp::forward_phase; confirmed from a kernel trace of these shapes on 256
   rowhead    Out <= 16, H <= 256 and the last hidden forward split-K (small batches on a wide input layer)
   generic    Out > 16, H > 256 or a single layer: loss_xent on the stored logits
 """
-import threading
-
 import numpy as np
 import pytest
 import torch
+
+from gpu_helpers import dev, host, run_ranks, shard
+from ref_mlp import XENT, hess_ref, loss_grad, objective, one_hot, rel
 
 pytestmark = pytest.mark.gpu
 
 LOSS_RTOL = 1e-5
 GRAD_RTOL = 1e-4
 HVP_RTOL = 1e-4
-ACTF = {"linear": lambda z: z, "relu": torch.relu, "tanh": torch.tanh, "sigmoid": torch.sigmoid}
-XENT = "softmax_xent"
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def host(t):
-    return t.double().cpu().numpy()
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
-
-
-def torch_obj(dims, acts, X, Y, inv_scale, lam, loss=XENT):
-    """The objective restated in torch (the style of test_gpu_hvp.py::torch_loss), in the dtype of X / Y."""
-    def f(P):
-        a, off = X, 0
-        for l in range(len(acts)):
-            i, o = dims[l], dims[l + 1]
-            W = P[off:off + i * o].reshape(i, o)
-            b = P[off + i * o:off + (i + 1) * o]
-            off += (i + 1) * o
-            a = ACTF[acts[l]](a @ W + b)
-        if loss == XENT:
-            data = (Y * (torch.logsumexp(a, 1, keepdim=True) - a)).sum()
-        else:
-            data = 0.5 * ((a - Y) ** 2).sum()
-        return inv_scale * data + 0.5 * lam * (P * P).sum()
-    return f
-
-
-def ref_loss_grad(dims, acts, P, X, Y, inv_scale, lam, dtype=torch.float64, loss=XENT):
-    f = torch_obj(dims, acts, torch.from_numpy(X).to(dtype), torch.from_numpy(Y).to(dtype), inv_scale, lam, loss)
-    p = torch.from_numpy(np.asarray(P)).to(dtype).requires_grad_(True)
-    l = f(p)
-    (g,) = torch.autograd.grad(l, p)
-    return float(l.detach()), g.double().numpy()
 
 
 def targets(rng, N, Out, soft):
     if soft:  # rows of rng.random, normalised
         Y = rng.random((N, Out))
         return (Y / Y.sum(1, keepdims=True)).astype(np.float32)
-    Y = np.zeros((N, Out), np.float32)
-    Y[np.arange(N), rng.integers(0, Out, N)] = 1.0
-    return Y
+    return one_hot(rng, N, Out)
 
 
 def check_loss_grad(ctx, pkg, dims, acts, X, Y, rows=None, l2=0.0, P=None, tag=""):
@@ -86,8 +44,8 @@ def check_loss_grad(ctx, pkg, dims, acts, X, Y, rows=None, l2=0.0, P=None, tag="
     B = len(sel)
     loss, g = net.loss_grad(P, dev(X), dev(Y), idx=idx, l2=l2)
     Ph = P.cpu().numpy()
-    l_ref, g_ref = ref_loss_grad(dims, acts, Ph, X[sel], Y[sel], 1.0 / B, l2)
-    _, g32 = ref_loss_grad(dims, acts, Ph, X[sel], Y[sel], 1.0 / B, l2, torch.float32)
+    l_ref, g_ref = loss_grad(dims, acts, XENT, Ph, X[sel], Y[sel], 1.0 / B, l2)
+    _, g32 = loss_grad(dims, acts, XENT, Ph, X[sel], Y[sel], 1.0 / B, l2, torch.float32)
     dl, dg, d32 = abs(loss - l_ref) / abs(l_ref), rel(host(g), g_ref), rel(g32, g_ref)
     print(f"xent {tag} {dims} B={B}: loss rel {dl:.2e}, grad rel {dg:.2e} (torch fp32: {d32:.2e})")
     assert np.isfinite(loss) and bool(torch.isfinite(g).all())
@@ -211,8 +169,8 @@ def test_hvp_matches_torch_fp64(ctx, pkg, dims, acts, lam, gather):
         idx = torch.from_numpy(rows.astype(np.int32)).cuda()
     B = len(rows)
     hv = net.hvp(P, v, dev(X), dev(Y), idx=idx, inv_scale=1.0 / B, l2=lam)
-    f = torch_obj(dims, acts, torch.from_numpy(X[rows]).double(), torch.from_numpy(Y[rows]).double(), 1.0 / B, lam)
-    _, ref = torch.autograd.functional.hvp(f, P.double().cpu(), v.double().cpu())
+    ref = hess_ref(dims, acts, XENT, P.double().cpu(), v.double().cpu(), torch.from_numpy(X[rows]).double(),
+                   torch.from_numpy(Y[rows]).double(), 1.0 / B, lam)
     err = float((hv.double().cpu() - ref).norm() / ref.norm())
     print(f"xent hvp {dims} lam={lam} gather={gather}: rel {err:.2e}")
     assert err <= HVP_RTOL
@@ -249,8 +207,8 @@ def test_fd_hvp_matches_torch_central_difference(ctx, pkg):
     v = torch.from_numpy(rng.standard_normal(net.nparams).astype(np.float32)).cuda()
     y_fd = host(net.fd_hvp(P, v, dev(X), dev(Y), inv_scale=1.0 / N, l2=1e-4, eps=eps))
     Ph, vh = host(P), host(v)
-    _, gp = ref_loss_grad(dims, acts, Ph + eps * vh, X, Y, 1.0 / N, 1e-4)
-    _, gm = ref_loss_grad(dims, acts, Ph - eps * vh, X, Y, 1.0 / N, 1e-4)
+    _, gp = loss_grad(dims, acts, XENT, Ph + eps * vh, X, Y, 1.0 / N, 1e-4)
+    _, gm = loss_grad(dims, acts, XENT, Ph - eps * vh, X, Y, 1.0 / N, 1e-4)
     err = rel(y_fd, (gp - gm) / (2 * eps))
     print(f"xent fd-hvp: rel {err:.2e}")
     assert err <= 2e-2
@@ -274,7 +232,7 @@ def test_lbfgs_matches_callback_objective(ctx, pkg, case, line_search):
     P = net.init_params(123, "cpu")
     Pf = P.clone()
     hist, _ = pkg.lbfgs_solve(net, P, dev(Xh), dev(Yh), line_search=line_search, m=5, max_iters=10, tol=0.0)
-    f = torch_obj(dims, acts, torch.from_numpy(Xh).double(), torch.from_numpy(Yh).double(), 1.0 / N, 0.0)
+    f = objective(dims, acts, XENT, torch.from_numpy(Xh).double(), torch.from_numpy(Yh).double(), 1.0 / N, 0.0)
 
     def fn(p, g):
         p64 = p.double().cpu().requires_grad_(True)
@@ -380,37 +338,6 @@ def test_shard_sum_equals_full_batch(ctx, pkg):
     assert rel(gs.cpu().numpy(), host(gf)) <= 1e-5
 
 
-def run_ranks(pkg, world, body, timeout=240):
-    """body(rank, ctx) on `world` threads, each rank of one in-process group on GPU 0 (as test_gpu_ranks.py)."""
-    ctxs = [pkg.Context(0, use_torch_stream=False) for _ in range(world)]
-    pkg.Context.comm_init_local(ctxs)
-    torch.cuda.synchronize()
-    out, err = [None] * world, [None] * world
-
-    def th(r):
-        try:
-            torch.cuda.set_device(0)
-            out[r] = body(r, ctxs[r])
-            torch.cuda.synchronize()
-        except BaseException as e:  # noqa: BLE001 (re-raised below)
-            err[r] = e
-
-    ts = [threading.Thread(target=th, args=(r,), daemon=True) for r in range(world)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join(timeout)
-    assert not any(t.is_alive() for t in ts), "a rank thread did not finish"
-    for e in err:
-        if e is not None:
-            raise e
-    return out
-
-
-def shard(N, world, r):
-    return N * r // world, N * (r + 1) // world
-
-
 def test_two_ranks_loss_grad_equals_single(ctx, pkg):
     dims, acts, N, world = [784, 128, 10], ["relu", "linear"], 4096, 2
     Xh, Yh = pkg.synth_mnist(N)
@@ -456,7 +383,7 @@ def _objective_at(dims, acts, P, Xh, Yh, lam, loss):
     """The torch fp64 objective at P, without and with the 0.5 lam ||w||^2 term."""
     X, Y = torch.from_numpy(Xh).double(), torch.from_numpy(Yh).double()
     p = P.double().cpu()
-    return [float(torch_obj(dims, acts, X, Y, 1.0 / len(Xh), l, loss)(p)) for l in (0.0, lam)]
+    return [float(objective(dims, acts, loss, X, Y, 1.0 / len(Xh), l)(p)) for l in (0.0, lam)]
 
 
 def _form(value, forms):
