@@ -369,9 +369,7 @@ int lbf_two_loop(lbf_ctx *ctx, long long n, int k, const float *d_S, const float
     LBF_HIP(hipMemsetAsync(zero.get(), 0, size_t(n) * sizeof(float), s));
     if (mode == 3) { // the S-LBFGS solver's own route (SlbfgsSolver::epoch_steps)
       LBF_REQUIRE(k <= DIR_MAXM && n % 4 == 0 && dir_supported(k, n) &&
-                      ((reinterpret_cast<uintptr_t>(d_g) | reinterpret_cast<uintptr_t>(d_dir)) & 15u) == 0 &&
-                      (k == 0 || ((reinterpret_cast<uintptr_t>(d_S) |
-                      reinterpret_cast<uintptr_t>(d_Y)) & 15u) == 0),
+                      aligned16(d_g, d_dir) && (k == 0 || aligned16(d_S, d_Y)),
                   "mode 3: k <= 16, n % 4 == 0, 16-B aligned vectors");
       for (int i = 0; i < k; ++i) { // pair updates: |y.s| > 1e-10, rho = 1 / y.s and the map K on the device
         GramArgs ga;

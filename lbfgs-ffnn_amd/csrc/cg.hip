@@ -20,7 +20,6 @@ namespace lbf {
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 constexpr int kCgMaxWg = 1024; // the cap of loss_partials_wg: 4 workgroups on each of 256 CUs, 1024-word tables
 
 // Elements [0, head) and [tail0, n) one at a time, [head, tail0) as nvec float4 groups.
@@ -29,12 +28,10 @@ struct Span {
 };
 
 template <class... P> Span make_span(long long n, P... ptrs) {
-  const uintptr_t a[] = {reinterpret_cast<uintptr_t>(ptrs)...};
-  bool same = true;
-  for (uintptr_t v : a) same = same && ((v & 15u) == (a[0] & 15u)) && ((v & 3u) == 0);
+  const int lead = common_lead(ptrs...);
   Span sp{n, n, 0, n};
-  if (same) {
-    sp.head = std::min<long long>(n, (long long)(((16u - (a[0] & 15u)) & 15u) / 4u));
+  if (lead >= 0) {
+    sp.head = std::min<long long>(n, lead);
     sp.nvec = (n - sp.head) / 4;
     sp.tail0 = sp.head + 4 * sp.nvec;
   }
@@ -47,14 +44,6 @@ __device__ __forceinline__ long long span_elem(const Span &sp, long long j) {
   return j < sp.head ? j : sp.tail0 + (j - sp.head);
 }
 
-// Block sum in a fixed order; every thread returns the same bits.
-__device__ __forceinline__ double block_sum_all(double q, double *wv) {
-  q = wave_sum_f64(q);
-  __syncthreads(); // wv may still be read from a previous sum
-  if ((threadIdx.x & 63) == 0) wv[threadIdx.x >> 6] = q;
-  __syncthreads();
-  return ((wv[0] + wv[1]) + wv[2]) + wv[3];
-}
 // The sum of a partial table, the same bits in every workgroup that calls it.
 __device__ __forceinline__ double table_sum(const double *t, int nwg, double *wv) {
   double q = 0.0;

@@ -24,8 +24,6 @@ namespace lbf {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // C columns per lane (64*C per block) as Q = C/4 quads, lane l owning columns 256q + 4l .. +3 of quad q;
 // VPW history vectors per wave (v = wave + 4j). GRED: a.gred_on (the deferred split-K reduction's 16 KB
 // of fp64 stripes in LDS are only declared where they are used, so the pair and sliced-DP sweeps keep the

@@ -26,7 +26,6 @@
 namespace lbf {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct GemmK {
   int M, N, K, k_chunk;
@@ -355,9 +354,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmK &g, f32x16 (&acc)[TM][
     if (g.head_fold > 0) hpre.store_fold(hs);
     KT(26);
     KTB(2);
-    headc::f32x4 cw[QM];
+    f32x4 cw[QM];
 #pragma unroll
-    for (int q = 0; q < QM; ++q) cw[q] = (headc::f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < QM; ++q) cw[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
     double sse = 0.0;
     headc::TileArgs ta;
     ta.Y = g.head_Y;
@@ -372,7 +371,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmK &g, f32x16 (&acc)[TM][
     headc::FoldAcc fa;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      fa.c[j] = (headc::f32x4){0.f, 0.f, 0.f, 0.f};
+      fa.c[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
       fa.db[j] = 0.0f;
     }
     for (int half = 0; half < (BM + TBR - 1) / TBR; ++half) {
@@ -1102,8 +1101,6 @@ __global__ __launch_bounds__(256 * KW, KW == 1 ? 2 : 1) void gemm_glds_group_ker
 
 namespace {
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 template <int BM, int BN> GemmK make_gemmk(const GemmDesc &d) {
   GemmK k;
   k.M = d.M;
@@ -1168,8 +1165,7 @@ template <int BM, int BN> GemmK make_gemmk(const GemmDesc &d) {
 template <int WM, int WN, int TM, int TN, bool AKC, bool BKC, int EPI, int KW = 1, int PF = 1, int NS = 0>
 void launch(hipStream_t s, const GemmDesc &d, const GemmDesc *d2 = nullptr) {
   // FAST loads: K % 4 == 0, vector-aligned operands, column counts % 4 == 0
-  const bool fast = d.K % 4 == 0 && (d.lda % 4 == 0) && (d.ldb % 4 == 0) &&
-                    ((reinterpret_cast<uintptr_t>(d.A) | reinterpret_cast<uintptr_t>(d.B)) & 15) == 0 &&
+  const bool fast = d.K % 4 == 0 && (d.lda % 4 == 0) && (d.ldb % 4 == 0) && aligned16(d.A, d.B) &&
                     (AKC || (d.a_mvalid > 0 ? d.a_mvalid : d.M) % 4 == 0) && (BKC || d.N % 4 == 0);
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   GemmK k = make_gemmk<BM, BN>(d);
@@ -1273,12 +1269,11 @@ bool gemm_asum_ok(const GemmDesc &d) {
   const int kc = d.splits > 1 ? d.k_chunk : d.K;
   return d.tile == TILE_32x128 && d.a_kc && !d.b_kc && !d.a_idx && (d.epi == EPI_STORE || d.epi == EPI_FWD) &&
          d.K % 4 == 0 && d.lda % 4 == 0 && d.ldb % 4 == 0 && d.a_slab_stride % 4 == 0 && kc > 0 && kc <= 4 * 32 &&
-         d.a_splits >= 1 && aligned16(d.A) && aligned16(d.B) && aligned16(d.a_slab) && aligned16(d.a_bias) &&
-         aligned16(d.a_out);
+         d.a_splits >= 1 && aligned16(d.A, d.B, d.a_slab, d.a_bias, d.a_out);
 }
 
 static bool glds_fast(const GemmDesc &d) { // launch()'s FAST conditions for mn-contiguous A and B
-  return d.K % 4 == 0 && d.lda % 4 == 0 && d.ldb % 4 == 0 && aligned16(d.A) && aligned16(d.B) &&
+  return d.K % 4 == 0 && d.lda % 4 == 0 && d.ldb % 4 == 0 && aligned16(d.A, d.B) &&
          (d.a_mvalid > 0 ? d.a_mvalid : d.M) % 4 == 0 && d.N % 4 == 0;
 }
 

@@ -30,8 +30,6 @@ namespace lbf {
 
 namespace headc {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int HMAX = 256;
 constexpr int HMAX_OUT = 16;
 constexpr int TB = 64;                     // samples per tile (4 strips of 16, one per wave)

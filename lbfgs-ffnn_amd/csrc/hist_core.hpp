@@ -1,4 +1,4 @@
-// Device-side history step shared by hist_step_kernel (vec_kernels.hip) and the fused optimizer tail
+// Device-side history step shared by hist_step_kernel (hist.hip) and the fused optimizer tail
 // (tail.hip): given the dots of the new pair / gradient against the live history, write the new
 // Gram rows, apply the pair acceptance rule of the policy (CPU lbfgs.hpp:77-84 ys > 1e-10; CUDA
 // lbfgs.cuh:160 ys > 1e-10; S-LBFGS s_lbfgs.hpp:253 |ys| > 1e-10), push/evict like
@@ -60,8 +60,6 @@ __device__ __forceinline__ int hist_write_slot(const int *ist, int m, int policy
   if (policy == POL_CUDA && count == m) return ist[IST_ORDER + 0];
   return ist[IST_FREE];
 }
-
-__device__ __forceinline__ double hc_wave_sum(double v) { return wave_sum_f64(v); }
 
 // Loads from the step's sources. LDS = true: the HistStep pointers are LDS copies, read with ds_read
 // (a generic pointer would be a flat load, whose wait also drains every global store in flight).
@@ -622,7 +620,7 @@ __device__ inline void hist_core(const HistStep &a, HistSmem &sm, double *sy, in
   double part = 0.0;
   if (lane < k) part += c0 * gS_l[lane] - gamma * al0 * gY_l[lane];
   if (lane + 64 < k) part += c1 * gS_l[lane + 64] - gamma * al1 * gY_l[lane + 64];
-  const double gTz = hc_wave_sum(part) + gamma * gg;
+  const double gTz = wave_sum_f64(part) + gamma * gg;
   // lbfgs.cuh:97-104 (CUDA semantics only): not a descent direction -> steepest descent + reset
   const bool fallback = a.policy == POL_CUDA && a.want_dir == 1 && ds * gTz >= 0.0;
   if (lane < k) {

@@ -77,9 +77,7 @@ bool History::update_impl(const GramArgs &g0, int want_dir, int iter, double dsi
   g.h = v_;
   g.h.abort = ctx_->abort;
   hipStream_t s = ctx_->stream;
-  auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-  const bool aligned = al16(g.sa) && al16(g.sb) && al16(g.ya) && al16(g.yb) && al16(g.ga) && al16(g.gb) &&
-                       al16(g.gc) && al16(g.g_out); // 16-B lanes in dir_sweep (null pointers pass)
+  const bool aligned = aligned16(g.sa, g.sb, g.ya, g.yb, g.ga, g.gb, g.gc, g.g_out); // 16-B lanes in dir_sweep
   const bool defer = gred && gred->nseg > 0;
   const bool dir = dir_on_ && aligned && g.policy == POL_SLBFGS && (want_dir == 0 || want_dir == 1);
   // the sweep reads a lane's four columns of a segment's slabs as one 16-B load per split
@@ -87,7 +85,7 @@ bool History::update_impl(const GramArgs &g0, int want_dir, int iter, double dsi
   for (int i = 0; defer && i < gred->nseg; ++i) {
     const RedSeg &S = gred->seg[i];
     quads = quads && S.goff % 4 == 0 && S.parts == 1 &&
-            (S.splits == 0 || (S.count % 4 == 0 && S.stride % 4 == 0 && al16(S.slab)));
+            (S.splits == 0 || (S.count % 4 == 0 && S.stride % 4 == 0 && aligned16(S.slab)));
   }
   const bool in_sweep = defer && dir && quads && g.has_g && !g.has_pair && gred->G == g.ga;
   if (defer && !in_sweep) { // only the fused sweep finishes deferred slabs

@@ -88,6 +88,19 @@ private:
 
 inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
 inline long long round4(long long n) { return cdiv(n, 4) * 4; }
+// Every pointer on a 16-byte boundary: the test in front of each float4 route. Null pointers pass (an absent
+// operand restricts nothing).
+template <class... P> inline bool aligned16(P... ptrs) {
+  return ((reinterpret_cast<uintptr_t>(static_cast<const void *>(ptrs)) | ...) & 15u) == 0;
+}
+// The scalar head of a float4 sweep over several vectors: the leading floats (0..3) that bring every pointer to a
+// 16-byte boundary when all are 4-byte aligned and share one offset from it; -1 otherwise (a scalar sweep).
+template <class... P> inline int common_lead(P... ptrs) {
+  const uintptr_t a[] = {reinterpret_cast<uintptr_t>(ptrs)...};
+  for (uintptr_t v : a)
+    if ((v & 15u) != (a[0] & 15u) || (v & 3u) != 0) return -1;
+  return int(((16u - (a[0] & 15u)) & 15u) / 4u);
+}
 inline int env_int(const char *name, int dflt) {
   const char *e = std::getenv(name);
   return e ? std::atoi(e) : dflt;
@@ -165,21 +178,11 @@ static __device__ unsigned long long lbf_kt_hw[1024];
     }                                                                                                   \
   } while (0)
 #else
-#define KTHW()                                                                                          \
-  do {                                                                                                  \
-  } while (0)
-#define KTF(slot)                                                                                       \
-  do {                                                                                                  \
-  } while (0)
-#define KTB(slot)                                                                                       \
-  do {                                                                                                  \
-  } while (0)
-#define KTC(slot)                                                                                       \
-  do {                                                                                                  \
-  } while (0)
-#define KT(slot)                                                                                        \
-  do {                                                                                                  \
-  } while (0)
+#define KTHW() ((void)0)
+#define KTF(slot) ((void)0)
+#define KTB(slot) ((void)0)
+#define KTC(slot) ((void)0)
+#define KT(slot) ((void)0)
 #endif
 
 } // namespace lbf

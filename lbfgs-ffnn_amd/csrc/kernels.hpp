@@ -1,4 +1,4 @@
-// Kernel launcher interfaces (implemented in gemm.hip / vec_kernels.hip) and the device-resident
+// Kernel launcher interfaces (each section names the .hip file that implements it) and the device-resident
 // L-BFGS history layout shared by host and device code.
 #pragma once
 
@@ -121,7 +121,7 @@ void gemm(hipStream_t s, const GemmDesc &d);
 void gemm_tile_for(int N, int tile, int *BM, int *BN);
 
 // ------------------------------------------------------------------------------------------------
-// Vector / reduction kernels (vec_kernels.hip). All reductions are deterministic: per-workgroup
+// Vector / reduction kernels (reduce.hip, loss.hip, blas1.hip). All reductions are deterministic: per-workgroup
 // fp64 partials written to memory, then summed in a fixed order by reduce_rows.
 // ------------------------------------------------------------------------------------------------
 // out[c] = sum_r P[r*ncols + c], r in [0, nrows), fixed order.    (one wave per column)
@@ -407,7 +407,7 @@ void scal(hipStream_t s, long long n, float alpha, float *x);
 // y = x + alpha * p; ww_part (nullable): also y's w.w partials (WwPart, ww_partials_n(n) words)
 void axpy_to(hipStream_t s, long long n, const float *x, float alpha, const float *p, float *y,
              double *ww_part = nullptr);
-// GD / SGD momentum step and SGD's device-side epoch-loss accumulator (vec_kernels.hip).
+// GD / SGD momentum step and SGD's device-side epoch-loss accumulator (blas1.hip).
 void momentum_step(hipStream_t s, long long n, float momentum, float lr, const float *lr_dev, const float *g, float *v,
                    float *x);
 void epoch_loss_acc(hipStream_t s, const double *scal, long long rows, float *esum);
@@ -437,7 +437,7 @@ void sum_ranks(hipStream_t s, const RankSrcs &r, long long count, float *dst);
 // Vectors s_i, y_i live in slots of S/Y (slots = m+1 so a rejected pair never clobbers live data);
 // the Gram matrices of all stored vectors are kept in fp64 and the two-loop recursion of the
 // reference runs on (2k+1) coefficients, so a direction costs two HBM sweeps of the history
-// (dots, then one linear combination) instead of 2k dependent dot/axpy launches.
+// (dots, then one linear combination) instead of 2k dependent dot/axpy launches. Kernels: hist.hip.
 // ------------------------------------------------------------------------------------------------
 enum HistPolicy : int { POL_CPU = 0, POL_CUDA = 1, POL_SLBFGS = 2 };
 

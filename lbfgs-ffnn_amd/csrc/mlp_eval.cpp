@@ -75,7 +75,7 @@ void Mlp::forward_phase(const float *P, const float *X, const float *Y, const in
   // the fold reads the last hidden layer's input with 16-byte loads; an unaligned caller X (2-layer
   // nets) takes the unfolded route instead
   const float *head_in = nl >= 3 ? A_[nl - 3].get() : X;
-  const int fold = (gemm_head && (reinterpret_cast<uintptr_t>(head_in) & 15u) == 0) ? fold_ : -1;
+  const int fold = (gemm_head && aligned16(head_in)) ? fold_ : -1;
   const bool row_head = fused && !gemm_head && rowhead_on(B);
   forward(P, X, idx, B, fused ? (gemm_head ? nl - 2 : nl - 1) : nl, row_head);
   int nloss, lstart;

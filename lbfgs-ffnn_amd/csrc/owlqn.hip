@@ -24,8 +24,6 @@ namespace lbf {
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 struct OwlMap {
   long long n, E;
   int vec, lead; // vec: float4 body after `lead` scalar elements of each workgroup
@@ -33,11 +31,8 @@ struct OwlMap {
 };
 
 template <class... P> OwlMap make_map(long long n, const OwlCoef &coef, P... ptrs) {
-  const uintptr_t a[] = {reinterpret_cast<uintptr_t>(ptrs)...};
-  bool same = true;
-  for (uintptr_t v : a) same = same && ((v & 15u) == (a[0] & 15u)) && ((v & 3u) == 0);
-  OwlMap m{n, ww_block_elems(n), same ? 1 : 0, same ? int(((16u - (a[0] & 15u)) & 15u) / 4u) : 0, coef};
-  return m;
+  const int lead = common_lead(ptrs...);
+  return OwlMap{n, ww_block_elems(n), lead >= 0 ? 1 : 0, lead >= 0 ? lead : 0, coef};
 }
 
 // The element ranges of workgroup blockIdx.x: [e0, a0) and [a1, e1) one at a time, [a0, a1) as nv float4 groups.
@@ -73,15 +68,6 @@ __device__ __forceinline__ long long owl_nscalar(const OwlMap &m, const OwlBlock
 __device__ __forceinline__ long long owl_scalar(const OwlMap &m, const OwlBlock &b, long long j) {
   if (!m.vec) return b.e0 + j;
   return j < b.a0 - b.e0 ? b.e0 + j : b.a1 + (j - (b.a0 - b.e0));
-}
-
-// Block sum in a fixed order; every thread returns the same bits.
-__device__ __forceinline__ double block_sum_all(double q, double *wv) {
-  q = wave_sum_f64(q);
-  __syncthreads(); // wv may still be read from a previous sum
-  if ((threadIdx.x & 63) == 0) wv[threadIdx.x >> 6] = q;
-  __syncthreads();
-  return ((wv[0] + wv[1]) + wv[2]) + wv[3];
 }
 
 // The pseudo-gradient of f + c |x| at one coordinate; each value is one fp32 add.

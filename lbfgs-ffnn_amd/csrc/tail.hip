@@ -26,10 +26,6 @@ namespace lbf {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double t_wave_sum(double v) { return wave_sum_f64(v); }
-
 // Barriers are LDS-only (wave.hpp lds_barrier): no thread reads global memory that another thread of
 // its block wrote in the same launch.
 //
@@ -267,7 +263,7 @@ __device__ __forceinline__ void tail_cols_body(const TailArgs &a, int abf) {
 #pragma unroll
     for (int u = 0; u < 8; ++u) s += (r0 + 256 * u < a.nb) ? v[u] : 0.0;
   }
-  s = t_wave_sum(s);
+  s = wave_sum_f64(s);
   if ((t & 63) == 0) ws[t >> 6] = s;
   lds_barrier();
   if (t == 0) {
@@ -325,7 +321,7 @@ __device__ __forceinline__ void tail_fin_body(const TailArgs &a) {
     alpha0 = sc[SC_ALPHA0];
     accept_prev = sc[SC_ACCEPT];
   }
-  sse = t_wave_sum(sse);
+  sse = wave_sum_f64(sse);
   if (lane == 0) v[wave] = sse;
   if constexpr (WW)
     if (lane == 0) wwv[wave] = wwq;
@@ -349,7 +345,7 @@ __device__ __forceinline__ void tail_fin_body(const TailArgs &a) {
     s_sc[2] = ww;
     s_sc[3] = sse_t;
     s_sc[4] = loss;
-    // ---- the line-search decision (ls_ctl_kernel's rule, vec_kernels.hip) ----
+    // ---- the line-search decision (ls_ctl_kernel's rule, loss.hip) ----
     const LsCtlArgs &L = a.ls;
     const double fn = loss;
     bool ok, conv;

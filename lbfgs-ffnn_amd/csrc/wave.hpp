@@ -1,4 +1,4 @@
-// Wavefront (64-lane) primitives shared by the kernels.
+// Wavefront (64-lane) primitives shared by the kernels, the workgroup sums built on them, and f32x4.
 //
 // wave_sum_f64: fixed-order fp64 reduction through DPP lane moves (quad_perm, row_half_mirror,
 // row_mirror, row_bcast15/31) — VALU moves instead of the ds_bpermute round trips a __shfl_xor
@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 
 namespace lbf {
+
+typedef float f32x4 __attribute__((ext_vector_type(4))); // one 16-byte lane access
 
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double dpp_f64(double v) {
@@ -49,6 +51,53 @@ __device__ __forceinline__ double ww_sum_fin(const double *v) { return ((v[0] + 
 // surrounding code is contracted to
 __device__ __forceinline__ double ww_loss(double data, double lambda, double ww) {
   return __fma_rn(__dmul_rn(0.5, lambda), ww, data);
+}
+// The loss of a point, 0.5 sse inv_scale + 0.5 lambda w.w, as every one-workgroup tail of reduce.hip forms it.
+// WW: w.w is the sum of the point's partials and ww_loss adds the penalty; else the plain expression, if lambda != 0.
+template <bool WW>
+__device__ __forceinline__ double point_loss(double sse, double inv_scale, double lambda, double ww) {
+  const double data = 0.5 * sse * inv_scale;
+  if constexpr (WW) return ww_loss(data, lambda, ww);
+  return lambda != 0.0 ? data + 0.5 * lambda * ww : data;
+}
+
+// The sum of a 256-thread block in a fixed order: wave sums, then ((v0 + v1) + v2) + v3; every thread returns the
+// same bits. wv: four doubles of LDS, which may still hold a previous sum.
+__device__ __forceinline__ double block_sum_all(double q, double *wv) {
+  q = wave_sum_f64(q);
+  __syncthreads(); // wv may still be read from a previous sum
+  if ((threadIdx.x & 63) == 0) wv[threadIdx.x >> 6] = q;
+  __syncthreads();
+  return ww_sum_fin(wv);
+}
+// One word of a w.w partial table (kernels.hpp WwPart): the 256-thread block's sum in block_sum_all's order,
+// stored by thread 0 with an ordinary store.
+__device__ __forceinline__ void ww_block_store(double q, double *part) {
+  __shared__ double wv[4];
+  q = wave_sum_f64(q);
+  if ((threadIdx.x & 63) == 0) wv[threadIdx.x >> 6] = q;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = ww_sum_fin(wv);
+}
+// Sum NV values over a 256- or 512-thread block; result valid in thread 0. scratch: NV*16 doubles.
+template <int NV>
+__device__ __forceinline__ void block_sum(double (&v)[NV], double *scratch) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) v[i] = wave_sum_f64(v[i]);
+  if (lane == 0)
+#pragma unroll
+    for (int i = 0; i < NV; ++i) scratch[i * 16 + wave] = v[i];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      double s = 0.0;
+      for (int w = 0; w < nw; ++w) s += scratch[i * 16 + w];
+      v[i] = s;
+    }
+  }
+  __syncthreads();
 }
 
 // Reductions over a DPP row (the 16 lanes l & ~15 .. l | 15): quad_perm [1,0,3,2] and [2,3,0,1], then

@@ -1,6 +1,6 @@
 // History-ring layout micro-benchmark (gfx950): does the slot stride of the (s, y) ring change the rate of the
 // combine sweep's many-stream read (2k vectors, 16 B per lane of each, fp64 accumulate, grid-stride over the
-// resident grid, nontemporal loads: vec_kernels.hip combine_kernel<8, true>) and of the Gram sweep's pattern
+// resident grid, nontemporal loads: then combine_kernel<8, true>, today hist.hip's combine_chunk_kernel) and of the Gram sweep's pattern
 // (one wave per vector over a 4096-float chunk, 4 quads in flight)?
 //   hipcc --offload-arch=gfx950 -O3 ring_ld.hip -o ring_ld && ./ring_ld
 // n = 10,489,857 (cfg 5), k = 100 vectors (m = 50). Strides: round4(n) (the engine's), + 64 / 256 / 1024 / 4160
