@@ -513,6 +513,83 @@ int  lbf_mlp_l1_trial(lbf_mlp *net, const float *d_x, const float *d_d, const fl
                       int l1_bias, float alpha, float *d_xnew, double *h_l1_term, double *h_ww,
                       double *h_dec /* pg.(xnew - x) */, long long *h_zeros);
 
+/* ---- Adam / AdamW over shuffled minibatches (extension; Kingma & Ba 2015, Loshchilov & Hutter 2019). New
+ * functions and structs only: LBF_ABI_VERSION stays 3.
+ *
+ * Minimises the objective of lbf_sgd_solve (the network's loss + 0.5 l2 |w|^2 with the network's l2, a mean over each
+ * batch). d_X / d_Y hold all N rows on every rank, as for lbf_slbfgs_solve. Epoch e = 0, 1, ..:
+ *   1. lr_e = lr, times decay_rate at every epoch e > 0 with e % decay_step == 0 (decay_step > 0), in fp64;
+ *   2. the epoch's order: the identity (shuffle == 0), else lbf_adam_epoch_orders' permutation e, all epochs drawn
+ *      from one mt19937(seed); batch k holds the positions [k batch, min((k + 1) batch, N)) of the order;
+ *   3. per batch, step t = 1, 2, .. counted over the whole solve: one fused evaluation of the batch (inv_scale =
+ *      1 / rows, the network's l2 inside the gradient), then one launch over the parameters with the nine fp32
+ *      coefficients of lbf_adam_coefs(prm, lr_e, t):
+ *        c   = 1, or clip_norm / ||g|| where ||g|| = sqrtf((float)(g.g)) > clip_norm   (clip_norm > 0)
+ *        gi  = g_i c;   m_i = b1 m_i + a1 gi;   v_i = b2 v_i + a2 (gi gi)
+ *        w_i = w_i decay - step (m_i / (sqrtf(v_i) rbc2 + eps))
+ *      every operation rounded once to fp32, m = v = 0 at the start. This is Adam with bias correction; decay =
+ *      1 - lr_e weight_decay is AdamW's decoupled decay, while the network's l2 is the coupled one. g.g is read on
+ *      the device from the evaluation's status block: no host synchronisation inside an epoch;
+ *   4. the epoch loss is sum_k (batch objective k) rows_k / N in fp64; when tol > 0 and a previous epoch exists the
+ *      solve stops once |prev - loss| / max(1, |prev|) < tol (lbf_sgd_solve's test; that epoch gets no record row);
+ *   5. with rec: one full-batch row (loss and gradient norm through float, like lbf_sgd_solve) for the start point
+ *      and one per epoch, alpha = lr_e.
+ * loss_trace (nullable, trace_cap entries): the batch objective of step t at [t - 1], evaluated before the step.
+ * info: iterations = the rows recorded (epochs, + 1 with rec), as lbf_sgd_solve counts; final_loss / final_grad_norm
+ * of the last full-batch row, or the last epoch loss and 0 without rec.
+ * With a communicator every rank takes positions [rows r / p, rows (r + 1) / p) of every batch (the split of
+ * LBF_SLBFGS_DP_SLICED; an empty slice is legal), the evaluation's all-reduce is the only collective of a step, and
+ * m, v and t are replicated: all ranks hold the same bits. The full-batch rows are sharded the same way.
+ * Non-finite gradients are outside the contract, as for lbf_sgd_solve.
+ * LBF_ERR_INVALID: null handles, batch < 1, lr <= 0, eps <= 0, beta1 or beta2 outside [0, 1), weight_decay or
+ * clip_norm negative or non-finite, decay_step < 0, max_epochs < 0, trace_cap < 0, N < 1 or N >= 2^31. */
+typedef struct lbf_adam_params {
+  double lr;               /* 1e-3  */
+  double beta1, beta2;     /* 0.9, 0.999 */
+  double eps;              /* 1e-8  */
+  double weight_decay;     /* 0: Adam; > 0: AdamW */
+  double clip_norm;        /* 0: off */
+  int batch;               /* 128   */
+  int shuffle;             /* 1     */
+  unsigned seed;           /* 123   */
+  double decay_rate;       /* 1.0, as lbf_sgd_params */
+  int decay_step;          /* 0: no decay */
+  int max_epochs;          /* 200   */
+  double tol;              /* 1e-6  */
+  double *loss_trace;      /* nullable */
+  int trace_cap;
+} lbf_adam_params;
+/* The step's coefficients, fp64 expressions rounded once to float (prm's fields in capitals):
+ *   b1 = BETA1, a1 = 1 - BETA1, b2 = BETA2, a2 = 1 - BETA2, step = lr_now / (1 - BETA1^t),
+ *   rbc2 = 1 / sqrt(1 - BETA2^t), eps = EPS, decay = 1 - lr_now WEIGHT_DECAY, clip = CLIP_NORM,
+ * with BETA^t the running product p_0 = 1, p_k = p_{k-1} BETA (t multiplications, no pow). */
+typedef struct lbf_adam_coef {
+  float b1, a1, b2, a2, step, rbc2, eps, decay, clip;
+} lbf_adam_coef;
+void lbf_adam_default_params(lbf_adam_params *p);
+/* Host only. LBF_ERR_INVALID: null pointers, t < 1, lr_now <= 0 or non-finite, or parameters lbf_adam_solve rejects. */
+int lbf_adam_coefs(const lbf_adam_params *prm, double lr_now, long long t, lbf_adam_coef *h_out);
+/* Host only: h_out[e N + i], e < epochs, the orders of epochs 0 .. epochs - 1 as the solver draws them: each starts
+ * from the identity and runs Fisher-Yates downward, for i = N - 1 .. 1: j = ((uint64)rng() (i + 1)) >> 32, swap
+ * positions i and j, rng one std::mt19937(seed) for all epochs, its raw 32-bit draws (no distribution object, so
+ * the orders do not depend on the standard library). j is uniform up to a bias of at most N / 2^32. */
+int lbf_adam_epoch_orders(long long N, unsigned seed, int epochs, int *h_out);
+/* The step of item 3 on device vectors of the caller's own (n floats each, 4-byte aligned, distinct). d_gg
+ * (nullable): a device double holding g.g; null or coef->clip == 0: no clipping. Asynchronous. */
+int lbf_adam_step(lbf_ctx *ctx, long long n, const lbf_adam_coef *coef, float *d_w, float *d_m, float *d_v,
+                  const float *d_g, const double *d_gg);
+int lbf_adam_solve(lbf_mlp *net, const lbf_adam_params *prm, float *d_params, const float *d_X, const float *d_Y,
+                   long long N, lbf_record *rec, lbf_solve_info *info);
+/* Stateful form: begin allocates m = v = 0 and records nothing yet; iterate runs up to `epochs` more epochs (fewer
+ * when the tol test stops the solve) with d_params updated in place; end releases the solver. begin +
+ * iterate(max_epochs) + end is lbf_adam_solve, and any chunking of the epochs gives the same bits. rec: pass a
+ * record to every iterate call or to none. h_epochs (nullable): the epochs completed so far. */
+typedef struct lbf_adam lbf_adam;
+int lbf_adam_begin(lbf_mlp *net, const lbf_adam_params *prm, float *d_params, const float *d_X, const float *d_Y,
+                   long long N, lbf_adam **out);
+int lbf_adam_iterate(lbf_adam *s, int epochs, lbf_record *rec, lbf_solve_info *info, int *h_epochs);
+int lbf_adam_end(lbf_adam *s);
+
 int lbf_slbfgs_solve(lbf_mlp *net, const lbf_slbfgs_params *prm, float *d_params, const float *d_X,
                      const float *d_Y, long long N, lbf_record *rec, lbf_solve_info *info);
 /* Stateful S-LBFGS (benchmarking, and callers that check progress between epochs): begin copies nothing

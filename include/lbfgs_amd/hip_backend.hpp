@@ -525,6 +525,67 @@ private:
   lbf_owlqn_stats stats_{};
 };
 
+/// Adam / AdamW minimizer on a HipNetwork (HIP extension, no reference counterpart: lbf_adam_solve, shuffled
+/// minibatches, one fused evaluation and one device-side sweep per step). Like HipHF, solve() minimises the
+/// network's own loss (+ its l2) and does not call loss_grad; n must be the network's parameter count, `batch` is the
+/// number of rows N of input / target, setMaxIterations counts epochs and setTolerance is the relative epoch-loss
+/// test of CudaSGD. With a recorder: the start point's full-batch row and one per epoch.
+class HipAdam : public HipMinimizerBase {
+public:
+  HipAdam(HipHandle &handle, HipNetwork &net) : HipMinimizerBase(handle), net_(net) { lbf_adam_default_params(&prm_); }
+  void setLearningRate(double lr) { prm_.lr = lr; }
+  void setBetas(double beta1, double beta2) {
+    prm_.beta1 = beta1;
+    prm_.beta2 = beta2;
+  }
+  void setEpsilon(double eps) { prm_.eps = eps; }
+  void setWeightDecay(double wd) { prm_.weight_decay = wd; } ///< AdamW's decoupled decay
+  void setClipNorm(double c) { prm_.clip_norm = c; }
+  void setBatchSize(int b) { prm_.batch = b; }
+  void setShuffle(bool on, unsigned seed = 123u) {
+    prm_.shuffle = on ? 1 : 0;
+    prm_.seed = seed;
+  }
+  void setLearningRateDecay(double rate, int step) {
+    prm_.decay_rate = rate;
+    prm_.decay_step = step;
+  }
+  /// the batch objective of every step of the last solve, evaluated before the step
+  const std::vector<double> &lossTrace() const { return trace_; }
+
+  void solve(int n, HipScalar *params, const HipScalar *input, const HipScalar *target, int batch,
+             const LossGradFun &) override {
+    if (n <= 0 || params == nullptr) {
+      last_iterations_ = 0;
+      return;
+    }
+    lbf_adam_params prm = prm_;
+    prm.max_epochs = max_iters_;
+    prm.tol = tol_;
+    const long long per_epoch = prm.batch > 0 ? (static_cast<long long>(batch) + prm.batch - 1) / prm.batch : 0;
+    trace_.assign(size_t(std::max(0LL, per_epoch * std::max(0, max_iters_))), std::nan(""));
+    prm.loss_trace = trace_.empty() ? nullptr : trace_.data();
+    prm.trace_cap = int(trace_.size());
+    lbf_record rec{};
+    lbf_record *rp = nullptr;
+    if (recorder_) {
+      recorder_->reset();
+      rec = recorder_->view();
+      rp = &rec;
+    }
+    lbf_solve_info info{};
+    hip_check(lbf_adam_solve(net_.raw(), &prm, params, input, target, batch, rp, &info), "lbf_adam_solve");
+    if (recorder_) recorder_->set_size(rec.size);
+    last_iterations_ = info.iterations;
+    while (!trace_.empty() && std::isnan(trace_.back())) trace_.pop_back(); // the steps that did not run
+  }
+
+private:
+  HipNetwork &net_;
+  lbf_adam_params prm_{};
+  std::vector<double> trace_;
+};
+
 /// Column-major host matrix with the subset of Eigen::MatrixXd's interface the launcher uses.
 class HostMatrix {
 public:
@@ -595,6 +656,11 @@ struct UnifiedConfig {
   double cg_rtol = 0.1;
   double damping = 1.0;
   double l1 = 0.0; ///< HIP extension: UnifiedOWLQN_HIP's L1 penalty on the weights; the other optimisers do not read it
+  /// HIP extension: UnifiedAdam_HIP (it also reads learning_rate, batch_size, max_iters as epochs, seed, and
+  /// lr_decay / lr_decay_rate when lr_decay > 0). weight_decay is AdamW's decoupled decay, clip_norm the global norm
+  /// each batch gradient is clipped to (0: off)
+  double beta1 = 0.9, beta2 = 0.999, adam_eps = 1e-8, weight_decay = 0.0, clip_norm = 0.0;
+  bool shuffle = true;
 };
 /// src/unified_optimization.hpp:54-59 (HostMatrix instead of Eigen::MatrixXd)
 struct UnifiedDataset {
@@ -831,6 +897,51 @@ public:
                                        &rec, &info, &stats),
                        "lbf_owlqn_solve");
     recorder.set_size(rec.size);
+    write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
+  }
+};
+
+/// Adam / AdamW (HIP extension, no reference counterpart): lbf_adam_solve with the config's learning_rate,
+/// batch_size, max_iters (epochs), seed and lr_decay / lr_decay_rate (only when lr_decay > 0) and, where the config is
+/// this header's own, its beta1, beta2, adam_eps, weight_decay, clip_norm and shuffle. The tolerance is not passed,
+/// as for UnifiedSGD_HIP. trace: the batch objective of every step.
+class UnifiedAdam_HIP : public UnifiedOptimizer<HipBackend> {
+public:
+  std::vector<double> trace;
+  void optimize(hip_mlp::HipHandle &, NetworkWrapper<HipBackend> &net, const UnifiedDataset &host_data,
+                hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dx, hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dy,
+                const UnifiedConfig &c) override {
+    const long n_train = long(host_data.train_x.cols());
+    auto &nw = net.getInternal();
+    lbf_adam_params prm;
+    lbf_adam_default_params(&prm);
+    prm.lr = c.learning_rate;
+    prm.batch = c.batch_size;
+    prm.max_epochs = c.max_iters;
+    prm.seed = c.seed;
+    if (c.lr_decay > 0.0) {
+      prm.decay_rate = c.lr_decay;
+      prm.decay_step = c.lr_decay_rate;
+    }
+#ifndef LBF_USE_REFERENCE_UNIFIED_TYPES // the reference's own UnifiedConfig has no such members
+    prm.beta1 = c.beta1;
+    prm.beta2 = c.beta2;
+    prm.eps = c.adam_eps;
+    prm.weight_decay = c.weight_decay;
+    prm.clip_norm = c.clip_norm;
+    prm.shuffle = c.shuffle ? 1 : 0;
+#endif
+    const long long per_epoch = prm.batch > 0 ? (static_cast<long long>(n_train) + prm.batch - 1) / prm.batch : 0;
+    trace.assign(size_t(std::max(0LL, per_epoch * std::max(0, c.max_iters))), std::nan(""));
+    prm.loss_trace = trace.empty() ? nullptr : trace.data();
+    prm.trace_cap = int(trace.size());
+    recorder.init(c.max_iters + 1);
+    lbf_record rec = recorder.view();
+    lbf_solve_info info{};
+    hip_mlp::hip_check(lbf_adam_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n_train, &rec, &info),
+                       "lbf_adam_solve");
+    recorder.set_size(rec.size);
+    while (!trace.empty() && std::isnan(trace.back())) trace.pop_back(); // the steps that did not run
     write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
   }
 };

@@ -82,6 +82,17 @@ class OwlqnStats(C.Structure):  # lbf_owlqn_stats
                 ("pg_norm", C.c_double)]
 
 
+class AdamParams(C.Structure):  # lbf_adam_params
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("clip_norm", C.c_double), ("batch", C.c_int), ("shuffle", C.c_int),
+                ("seed", C.c_uint), ("decay_rate", C.c_double), ("decay_step", C.c_int), ("max_epochs", C.c_int),
+                ("tol", C.c_double), ("loss_trace", C.POINTER(C.c_double)), ("trace_cap", C.c_int)]
+
+
+class AdamCoef(C.Structure):  # lbf_adam_coef
+    _fields_ = [(k, C.c_float) for k in ("b1", "a1", "b2", "a2", "step", "rbc2", "eps", "decay", "clip")]
+
+
 class Record(C.Structure):
     _fields_ = [("loss", C.POINTER(C.c_double)), ("grad_norm", C.POINTER(C.c_double)),
                 ("time_ms", C.POINTER(C.c_double)), ("alpha", C.POINTER(C.c_double)),
@@ -204,6 +215,15 @@ def lib():
         "lbf_mlp_l1_pseudo_grad": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_int, _vp, C.POINTER(OwlqnStats)]),
         "lbf_mlp_l1_trial": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_int, C.c_float, _vp, _dp, _dp, _dp,
                                        C.POINTER(C.c_longlong)]),
+        "lbf_adam_default_params": (None, [C.POINTER(AdamParams)]),
+        "lbf_adam_coefs": (C.c_int, [C.POINTER(AdamParams), C.c_double, C.c_longlong, C.POINTER(AdamCoef)]),
+        "lbf_adam_epoch_orders": (C.c_int, [C.c_longlong, C.c_uint, C.c_int, _vp]),
+        "lbf_adam_step": (C.c_int, [_vp, C.c_longlong, C.POINTER(AdamCoef), _vp, _vp, _vp, _vp, _vp]),
+        "lbf_adam_solve": (C.c_int, [_vp, C.POINTER(AdamParams), _vp, _vp, _vp, C.c_longlong, C.POINTER(Record),
+                                     C.POINTER(SolveInfo)]),
+        "lbf_adam_begin": (C.c_int, [_vp, C.POINTER(AdamParams), _vp, _vp, _vp, C.c_longlong, C.POINTER(_vp)]),
+        "lbf_adam_iterate": (C.c_int, [_vp, C.c_int, C.POINTER(Record), C.POINTER(SolveInfo), _ip]),
+        "lbf_adam_end": (C.c_int, [_vp]),
         "lbf_mlp_evaluate": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_int, C.c_longlong,
                                        C.POINTER(EvalResultC), _vp, _vp, _vp]),
     }
@@ -227,7 +247,9 @@ EXPORTS = ("lbf_last_error lbf_version lbf_abi_version lbf_ctx_create lbf_ctx_de
            "lbf_mlp_set_loss lbf_mlp_get_loss lbf_mlp_set_l2 lbf_mlp_get_l2 lbf_mlp_evaluate lbf_mlp_gnvp "
            "lbf_cg_default_params lbf_mlp_gn_cg lbf_mlp_gn_cg_residual lbf_hf_default_params lbf_hf_solve "
            "lbf_owlqn_default_params lbf_owlqn_solve lbf_mlp_l1_pseudo_grad lbf_mlp_l1_trial "
-           "lbf_mlp_grad_sq lbf_mlp_gn_pcg lbf_hf_precond_default lbf_hf_solve_pc").split()
+           "lbf_mlp_grad_sq lbf_mlp_gn_pcg lbf_hf_precond_default lbf_hf_solve_pc "
+           "lbf_adam_default_params lbf_adam_coefs lbf_adam_epoch_orders lbf_adam_step lbf_adam_solve lbf_adam_begin "
+           "lbf_adam_iterate lbf_adam_end").split()
 
 
 def check_precond(name) -> int:

@@ -717,6 +717,101 @@ int lbf_mlp_l1_trial(lbf_mlp *net, const float *d_x, const float *d_d, const flo
   });
 }
 
+void lbf_adam_default_params(lbf_adam_params *p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->lr = 1e-3;
+  p->beta1 = 0.9;
+  p->beta2 = 0.999;
+  p->eps = 1e-8;
+  p->batch = 128;
+  p->shuffle = 1;
+  p->seed = 123;
+  p->decay_rate = 1.0; // lbf_sgd_default_params
+  p->max_epochs = 200;
+  p->tol = 1e-6;
+}
+
+int lbf_adam_coefs(const lbf_adam_params *prm, double lr_now, long long t, lbf_adam_coef *h_out) {
+  return guard([&] {
+    LBF_REQUIRE(prm && h_out, "null argument");
+    adam_check(*prm);
+    LBF_REQUIRE(t >= 1 && std::isfinite(lr_now) && lr_now > 0.0, "t >= 1, lr_now finite and > 0");
+    double p1 = 1.0, p2 = 1.0; // the solver's running products: one multiplication per step
+    for (long long i = 0; i < t; ++i) {
+      p1 *= prm->beta1;
+      p2 *= prm->beta2;
+    }
+    const AdamCoef k = adam_coefs(*prm, lr_now, p1, p2);
+    std::memcpy(h_out, &k, sizeof(k));
+  });
+}
+
+int lbf_adam_epoch_orders(long long N, unsigned seed, int epochs, int *h_out) {
+  return guard([&] {
+    LBF_REQUIRE(N >= 1 && N < (1LL << 31) && epochs >= 0 && h_out, "bad argument");
+    std::mt19937 rng(seed);
+    for (int e = 0; e < epochs; ++e) epoch_order(rng, N, h_out + size_t(e) * size_t(N));
+  });
+}
+
+int lbf_adam_step(lbf_ctx *ctx, long long n, const lbf_adam_coef *coef, float *d_w, float *d_m, float *d_v,
+                  const float *d_g, const double *d_gg) {
+  return guard([&] {
+    LBF_REQUIRE(ctx && coef && d_w && d_m && d_v && d_g && n >= 0, "bad argument");
+    ctx->c.set_device();
+    AdamCoef k;
+    std::memcpy(&k, coef, sizeof(k));
+    adam_step(ctx->c.stream, n, k, d_g, d_m, d_v, d_w, d_gg);
+  });
+}
+
+struct lbf_adam {
+  std::unique_ptr<AdamSolver> s;
+};
+
+int lbf_adam_begin(lbf_mlp *net, const lbf_adam_params *prm, float *d_params, const float *d_X, const float *d_Y,
+                   long long N, lbf_adam **out) {
+  return guard([&] {
+    LBF_REQUIRE(prm && out, "null argument");
+    adam_check(*prm);
+    LBF_REQUIRE(N >= 1 && N < (1LL << 31), "N must lie in [1, 2^31)");
+    LBF_REQUIRE(net && d_params && d_X && d_Y, "null argument");
+    net->ctx->c.set_device();
+    auto *h = new lbf_adam();
+    try {
+      h->s.reset(new AdamSolver(net->net.get(), *prm, d_params, d_X, d_Y, N));
+    } catch (...) {
+      delete h;
+      throw;
+    }
+    *out = h;
+  });
+}
+
+int lbf_adam_iterate(lbf_adam *s, int epochs, lbf_record *rec, lbf_solve_info *info, int *h_epochs) {
+  return guard([&] {
+    LBF_REQUIRE(s && epochs >= 0, "bad argument");
+    s->s->iterate(epochs, rec);
+    s->s->info(info);
+    if (h_epochs) *h_epochs = s->s->epochs();
+  });
+}
+
+int lbf_adam_end(lbf_adam *s) {
+  return guard([&] { delete s; });
+}
+
+int lbf_adam_solve(lbf_mlp *net, const lbf_adam_params *prm, float *d_params, const float *d_X, const float *d_Y,
+                   long long N, lbf_record *rec, lbf_solve_info *info) {
+  lbf_adam *s = nullptr;
+  int r = lbf_adam_begin(net, prm, d_params, d_X, d_Y, N, &s);
+  if (r != LBF_OK) return r;
+  r = lbf_adam_iterate(s, prm->max_epochs, rec, info, nullptr);
+  lbf_adam_end(s);
+  return r;
+}
+
 void lbf_slbfgs_default_params(lbf_slbfgs_params *p) {
   if (!p) return;
   p->max_epochs = 1000; // stochastic_minimizer.hpp:44-47

@@ -411,6 +411,25 @@ void axpy_to(hipStream_t s, long long n, const float *x, float alpha, const floa
 void momentum_step(hipStream_t s, long long n, float momentum, float lr, const float *lr_dev, const float *g, float *v,
                    float *x);
 void epoch_loss_acc(hipStream_t s, const double *scal, long long rows, float *esum);
+// The Adam / AdamW step in one launch (adam.hip; the solver is AdamSolver, solve_adam.cpp). The nine
+// coefficients are the fields of lbf_adam_coef (lbfgs_amd.h), formed on the host once per step. Per element, each
+// operation rounded once and none contracted:
+//   gi = g c;  m = b1 m + a1 gi;  v = b2 v + a2 (gi gi);  w = w decay - step (m / (sqrt(v) rbc2 + eps))
+// c = 1 when gg is null or clip == 0; else nrm = sqrt(float(*gg)) and c = clip / nrm where nrm > clip, so the
+// gradient is clipped to the global norm `clip` from the evaluation's device-side g.g, with no host read.
+// ls (scal non-null): thread 0 also adds scal[SC_LOSS] * rows to the fp64 epoch sum *esum and stores scal[SC_LOSS]
+// in *trace (nullable). g, m, v, w: n floats, 4-byte aligned, distinct; float4 when all four share their offset
+// from a 16-byte boundary.
+struct AdamCoef {
+  float b1, a1, b2, a2, step, rbc2, eps, decay, clip;
+};
+struct AdamLoss {
+  const double *scal = nullptr;
+  double rows = 0.0;
+  double *esum = nullptr, *trace = nullptr;
+};
+void adam_step(hipStream_t s, long long n, const AdamCoef &k, const float *g, float *m, float *v, float *w,
+               const double *gg, const AdamLoss &ls = {});
 // u = (sum_i W[slot_i]) / cnt  in logical order, fp64 accumulation
 void average_slots(hipStream_t s, long long n, const float *W, long long ld, const int *h_slots, int cnt, float *u);
 // out = a + c*b

@@ -28,6 +28,15 @@ size_t MinibatchSampler::draw(size_t b, std::mt19937 &rng, std::vector<int> &out
   return b;
 }
 
+void epoch_order(std::mt19937 &rng, long long N, int *out) {
+  for (long long i = 0; i < N; ++i) out[i] = int(i);
+  for (long long i = N - 1; i >= 1; --i) {
+    const unsigned long long r = (unsigned long long)(rng() & 0xffffffffu);
+    const long long j = (long long)((r * (unsigned long long)(i + 1)) >> 32);
+    std::swap(out[i], out[j]);
+  }
+}
+
 std::vector<size_t> sample_minibatch(size_t N, size_t b, std::mt19937 &rng) {
   MinibatchSampler smp(N);
   std::vector<int> v;

@@ -22,4 +22,17 @@ class MinibatchSampler {
 // One draw with a fresh sampler (the ABI helper).
 std::vector<size_t> sample_minibatch(size_t N, size_t b, std::mt19937 &rng);
 
+// Rank rk's share of a batch of `total` positions split over nr ranks: [a0, a1) = [total rk / nr, total (rk + 1) / nr).
+// The one definition of the sliced split (S-LBFGS LBF_SLBFGS_DP_SLICED, Adam); a share may be empty.
+inline void rank_slice(long long total, int rk, int nr, long long *a0, long long *a1) {
+  *a0 = total * rk / nr;
+  *a1 = total * (rk + 1) / nr;
+}
+
+// An epoch's order of the Adam solver: out[0 .. N) = the identity, then Fisher-Yates downward, for i = N - 1 .. 1:
+// j = (uint64(rng()) * (i + 1)) >> 32, swap out[i], out[j]. Raw 32-bit draws and no uniform_int_distribution, so the
+// order is a function of the mt19937 stream alone, whatever the standard library; j is uniform up to a bias of at
+// most N / 2^32. One draw per position: successive epochs continue one stream.
+void epoch_order(std::mt19937 &rng, long long N, int *out);
+
 } // namespace lbf

@@ -238,7 +238,8 @@ void SlbfgsSolver::draw_epoch(bool u_seen, EpochDraw &d) {
   auto take = [&](size_t bsz, std::vector<int> &dst) {
     d.batch.clear();
     const long long tot = (long long)sampler_->draw(bsz, rng_, d.batch);
-    const long long a0 = tot * rk / nr, a1 = tot * (rk + 1) / nr;
+    long long a0, a1;
+    rank_slice(tot, rk, nr, &a0, &a1);
     Slice sl{(long long)dst.size(), a1 - a0, tot};
     dst.insert(dst.end(), d.batch.begin() + a0, d.batch.begin() + a1);
     return sl;

@@ -1,5 +1,5 @@
 // Solver drivers (solve_*.cpp): full-batch L-BFGS (CPU/Wolfe and CUDA/Armijo semantics), S-LBFGS, GD, SGD,
-// Hessian-free and OWL-QN.
+// Hessian-free, OWL-QN and Adam.
 #pragma once
 
 #include "../../include/lbfgs_amd.h"
@@ -342,6 +342,47 @@ int run_gd(Mlp *net, const lbf_gd_params &prm, float *d_params, const float *X, 
            long long n_global, lbf_record *rec, lbf_solve_info *info);
 int run_sgd(Mlp *net, const lbf_sgd_params &prm, float *d_params, const float *X, const float *Y, long long N,
             lbf_record *rec, lbf_solve_info *info);
+
+// Adam / AdamW over shuffled minibatches (lbfgs_amd.h lbf_adam_solve states the algorithm). The host
+// forms the step's nine coefficients (adam_coefs), draws the epoch's order and enqueues, per batch, the fused
+// evaluation and one sweep (adam.hip) that also accumulates the epoch loss: one synchronisation per epoch.
+// adam_check: LBF_ERR_INVALID for parameters outside the contract. adam_coefs: p1, p2 = beta1^t, beta2^t, the
+// caller's running fp64 products.
+void adam_check(const lbf_adam_params &prm);
+AdamCoef adam_coefs(const lbf_adam_params &prm, double lr_now, double p1, double p2);
+class AdamSolver {
+public:
+  AdamSolver(Mlp *net, const lbf_adam_params &prm, float *d_params, const float *X, const float *Y, long long N);
+  int iterate(int epochs, lbf_record *rec); // up to `epochs` more; returns the epochs run
+  void info(lbf_solve_info *out) const;
+  int epochs() const { return epoch_; }
+
+private:
+  void full_record(bool start);
+  Mlp *net_;
+  Ctx *ctx_;
+  lbf_adam_params prm_;
+  float *w_;
+  const float *X_, *Y_;
+  long long N_, n_, nb_;
+  double l2_;
+  DevBuf<float> g_, m_, v_;
+  DevBuf<double> scal_, acc_; // acc_: [epoch sum | one batch objective per step of the epoch]
+  PinnedBuf<double> hacc_;
+  DevBuf<int> idx_;
+  PinnedBuf<int> hidx_;
+  std::vector<int> order_;
+  std::mt19937 rng_;
+  StatusMirror hs_;
+  RecordWriter rw_; // begun from rec->size by the first iterate() only
+  SolveCounters<Mlp> cnt_;
+  std::chrono::steady_clock::time_point t0_;
+  long long t_ = 0;             // steps so far
+  double p1_ = 1.0, p2_ = 1.0;  // beta1^t, beta2^t
+  double lr_e_ = 0.0, prev_ = 0.0;
+  int epoch_ = 0, rows_done_ = 0;
+  bool started_ = false, have_prev_ = false, converged_ = false, recorded_ = false;
+};
 
 // Hessian-free solver (lbfgs_amd.h lbf_hf_solve): Gauss-Newton CG steps with Levenberg-Marquardt
 // damping and a backtracking line search; returns the outer iterations done.

@@ -4,3 +4,4 @@
 #include "loss.hip"
 #include "blas1.hip"
 #include "hist.hip"
+#include "adam.hip"

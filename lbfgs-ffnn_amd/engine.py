@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from ._lib import (ACTS, HVP_MODES, INIT_CPU, INIT_CUDA, LOSSES, PRECONDS, HfPrecond, check_l2, check_precond, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED, SLBFGS_DP_SLICED,
-                   CgInfo, CgParams, EvalResultC, GdParams, HfParams, LbfError, LbfgsParams, OwlqnParams, OwlqnStats, Record, SgdParams, SlbfgsParams, SolveInfo, check, lib,
+                   AdamCoef, AdamParams, CgInfo, CgParams, EvalResultC, GdParams, HfParams, LbfError, LbfgsParams, OwlqnParams, OwlqnStats, Record, SgdParams, SlbfgsParams, SolveInfo, check, lib,
                    ptr)
 
 _check_rc = check  # for Mlp.gn_cg, whose `check` argument is the CG status-read interval
@@ -87,6 +87,16 @@ class Context:
                                  C.cast(rho_arr, C.POINTER(C.c_double)) if k else None, ptr(g), ptr(out), mode),
               "lbf_two_loop")
         return out
+
+    def adam_step(self, w: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tensor, coef: AdamCoef,
+                  gg: Optional[torch.Tensor] = None):
+        """One Adam / AdamW step in place on w, m, v with gradient g (lbf_adam_step): float32 vectors of one length,
+        coef from adam_coefs. gg (a float64 device tensor of one element holding g.g) clips g to the global norm
+        coef.clip; None or coef.clip == 0: no clipping. Asynchronous on the context stream."""
+        n = int(w.numel())
+        check(lib().lbf_adam_step(self.h, n, C.byref(coef), ptr(w), ptr(m, numel=n), ptr(v, numel=n), ptr(g, numel=n),
+                                  ptr(gg, torch.float64, 1)), "lbf_adam_step")
+        return w
 
     PROF_KINDS = ["gemm_fwd", "gemm_dw", "gemm_dx", "loss", "splitk_reduce", "finalize", "gram_sweep",
                   "hist_coef", "combine_sweep", "ls_axpy", "allreduce", "metrics", "owl_pseudo", "owl_trial"]
@@ -448,6 +458,13 @@ class Mlp:
                                          C.byref(ww), C.byref(dec), C.byref(zeros)), "lbf_mlp_l1_trial")
         return out, {"l1_term": l1t.value, "ww": ww.value, "dec": dec.value, "zeros": zeros.value}
 
+    def adam_step(self, params: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tensor, coef: AdamCoef,
+                  gg: Optional[torch.Tensor] = None):
+        """Context.adam_step on this network's parameters: for callers that evaluate with loss_grad and keep
+        their own m and v (nparams floats each)."""
+        ptr(params, numel=self.nparams)   # the length check; the vectors must match it
+        return self.ctx.adam_step(params, m, v, g, coef, gg)
+
     def fd_hvp(self, params: torch.Tensor, v: torch.Tensor, X: torch.Tensor, Y: torch.Tensor,
                idx: Optional[torch.Tensor] = None, inv_scale: Optional[float] = None, l2: float = 0.0,
                eps: float = 1e-4, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -800,6 +817,110 @@ def owlqn_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor
     stats = {k: getattr(st, k) for k, _ in OwlqnStats._fields_}
     stats["zeros_trace"] = trace[:int(info.iterations)]
     return hist.as_dict(), info, stats
+
+
+def adam_params(**kw) -> AdamParams:
+    """lbf_adam_params with the library's defaults and the given fields (lr, beta1, beta2, eps, weight_decay,
+    clip_norm, batch, shuffle, seed, decay_rate, decay_step, max_epochs, tol); the trace pointer is adam_solve's.
+    An unknown keyword raises LbfError."""
+    p = AdamParams()
+    lib().lbf_adam_default_params(C.byref(p))
+    settable = {k for k, _ in AdamParams._fields_} - {"loss_trace", "trace_cap"}
+    for k, v in kw.items():
+        if k not in settable:
+            raise LbfError(f"adam_params: unknown parameter {k!r} (known: {', '.join(sorted(settable))})")
+        if v is not None:
+            setattr(p, k, int(v) if k == "shuffle" else v)
+    return p
+
+
+def adam_coefs(p: AdamParams, lr_now: float, t: int) -> AdamCoef:
+    """The nine fp32 coefficients of step t at learning rate lr_now (lbf_adam_coefs; host only)."""
+    k = AdamCoef()
+    check(lib().lbf_adam_coefs(C.byref(p), float(lr_now), int(t), C.byref(k)), "lbf_adam_coefs")
+    return k
+
+
+def adam_epoch_orders(N: int, seed: int = 123, epochs: int = 1) -> np.ndarray:
+    """The row orders of epochs 0 .. epochs - 1 as adam_solve draws them with shuffle=1 (lbf_adam_epoch_orders; host
+    only): int32 [epochs][N], each row a permutation of 0 .. N - 1."""
+    out = np.empty((int(epochs), int(N)), np.int32)
+    check(lib().lbf_adam_epoch_orders(int(N), int(seed), int(epochs), out.ctypes.data_as(C.c_void_p)),
+          "lbf_adam_epoch_orders")
+    return out
+
+
+def _adam_trace(p: AdamParams, N: int, epochs: int):
+    steps = max(1, int(epochs) * -(-int(N) // max(int(p.batch), 1)))
+    trace = np.full(steps, np.nan)
+    p.loss_trace = trace.ctypes.data_as(C.POINTER(C.c_double))
+    p.trace_cap = steps
+    return trace
+
+
+def adam_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, record: bool = True, **kw):
+    """Adam / AdamW over shuffled minibatches (lbf_adam_solve) on the network's loss + its l2; params updated in
+    place, X / Y hold all N rows on every rank. kw: see adam_params (weight_decay > 0 is AdamW's decoupled decay,
+    clip_norm > 0 clips each batch gradient to that global norm). record=False runs without the full-batch rows.
+    Returns (hist, info, trace): trace[t] is the batch objective evaluated before step t + 1."""
+    p = adam_params(**kw)
+    net._check_data(X, Y)
+    N = int(X.shape[0])
+    trace = _adam_trace(p, N, p.max_epochs)
+    hist = History(p.max_epochs + 1)
+    info = SolveInfo()
+    check(lib().lbf_adam_solve(net.h, C.byref(p), ptr(params, numel=net.nparams), ptr(X), ptr(Y), N,
+                               C.byref(hist.rec) if record else None, C.byref(info)), "lbf_adam_solve")
+    return hist.as_dict(), info, trace[~np.isnan(trace)]
+
+
+class _Epochs:
+    """What AdamRun.iterate returns: `iterations` counts epochs, as LbfgsRun / SlbfgsRun count their iterations
+    (lbf_solve_info.iterations of the Adam solver counts record rows, like lbf_sgd_solve's)."""
+
+    def __init__(self, iterations: int):
+        self.iterations = int(iterations)
+
+
+class AdamRun:
+    """Stateful Adam (lbf_adam_begin / iterate / end): the epochs of one solve across several iterate() calls,
+    bitwise one adam_solve. max_epochs bounds the loss trace only; iterate() decides how many epochs run."""
+
+    def __init__(self, net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, record_cap: int = 100000,
+                 **kw):
+        self.p = adam_params(**kw)
+        net._check_data(X, Y)
+        N = int(X.shape[0])
+        self.trace = _adam_trace(self.p, N, self.p.max_epochs)
+        self.hist = History(record_cap)
+        self.info = SolveInfo()
+        self.epochs = 0
+        self._keep = (net, params, X, Y)
+        h = C.c_void_p()
+        check(lib().lbf_adam_begin(net.h, C.byref(self.p), ptr(params, numel=net.nparams), ptr(X), ptr(Y), N,
+                                   C.byref(h)), "lbf_adam_begin")
+        self.h = h
+
+    def iterate(self, epochs: int):
+        done = C.c_int(0)
+        check(lib().lbf_adam_iterate(self.h, int(epochs), C.byref(self.hist.rec), C.byref(self.info), C.byref(done)),
+              "lbf_adam_iterate")
+        self.epochs = int(done.value)
+        return _Epochs(self.epochs)
+
+    def loss_trace(self):
+        return self.trace[~np.isnan(self.trace)]
+
+    def close(self):
+        if self.h:
+            lib().lbf_adam_end(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def sgd_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, record: bool = True, **kw):

@@ -62,12 +62,20 @@ class UnifiedConfig:
     curv_rows: int = 0
     precond: str = "none"        # UnifiedHF's CG preconditioner: "none" or "grad_sq" (the squared-gradient diagonal)
     precond_exponent: float = 0.75
-    # Validation-monitored training (HIP extension; UnifiedLBFGS and UnifiedSLBFGS). eval_every > 0: the test split
+    # Validation-monitored training (HIP extension; UnifiedLBFGS, UnifiedSLBFGS and UnifiedAdam). eval_every > 0: the test split
     # is evaluated on the device at iteration 0, every eval_every iterations (epochs for S-LBFGS) and at the end.
     eval_every: int = 0          # 0: off (the unmonitored code path)
     patience: int = 0            # stop after this many evaluations in a row without a strict improvement; 0: never
     monitor: str = "loss"        # "loss" (lower is better) or "accuracy" (higher is better)
     restore_best: bool = True    # finish with the parameters of the best evaluation
+    # UnifiedAdam (HIP extension): it also reads learning_rate, batch_size, max_iters (epochs), seed (the shuffle's),
+    # lr_decay / lr_decay_rate (applied only when lr_decay > 0) and the network's l2 (the coupled penalty)
+    beta1: float = 0.9
+    beta2: float = 0.999
+    adam_eps: float = 1e-8
+    weight_decay: float = 0.0    # AdamW's decoupled decay
+    clip_norm: float = 0.0       # clip each batch gradient to this global norm; 0: off
+    shuffle: bool = True         # a fresh row order per epoch; False: contiguous batches like UnifiedSGD
 
 
 @dataclass
@@ -232,7 +240,7 @@ def _assert_ranks_agree(entry) -> None:
 
 
 def _monitored_run(optimizer: "UnifiedOptimizer", net: _DeviceNet, data: "_DeviceData", config: UnifiedConfig, run):
-    """Drive a resumable solver (`run`: LbfgsRun / SlbfgsRun on net.mlp) in chunks of config.eval_every iterations,
+    """Drive a resumable solver (`run`: LbfgsRun / SlbfgsRun / AdamRun on net.mlp) in chunks of config.eval_every iterations,
     evaluating the test split between the chunks on a second Mlp of the same shape (the solver's own network and
     workspace are never touched). Sets optimizer.validation = [(iteration, val_loss, val_accuracy)],
     optimizer.best_iteration and optimizer.stopped_early; with restore_best the best parameters are copied back."""
@@ -335,7 +343,7 @@ class UnifiedGD(UnifiedOptimizer):
 
     def optimize(self, net, data, config):
         if config.eval_every > 0:
-            raise LbfError("UnifiedGD has no resumable form: eval_every > 0 needs UnifiedLBFGS or UnifiedSLBFGS")
+            raise LbfError("UnifiedGD has no resumable form: eval_every > 0 needs UnifiedLBFGS, UnifiedSLBFGS or UnifiedAdam")
         hist, info = engine.gd_solve(net.mlp, net.params, data.x, data.y, n_global=data.n_global,
                                      lr=config.learning_rate, momentum=config.momentum, max_iters=config.max_iters,
                                      tol=config.tolerance)
@@ -355,7 +363,7 @@ class UnifiedHF(UnifiedOptimizer):
 
     def optimize(self, net, data, config):
         if config.eval_every > 0:
-            raise LbfError("UnifiedHF has no resumable form: eval_every > 0 needs UnifiedLBFGS or UnifiedSLBFGS")
+            raise LbfError("UnifiedHF has no resumable form: eval_every > 0 needs UnifiedLBFGS, UnifiedSLBFGS or UnifiedAdam")
         engine.hf_precond(config.precond, config.precond_exponent)   # an unknown name fails here, before the device
         precond = None if config.precond == "none" else config.precond   # "none": lbf_hf_solve itself
         hist, info, traces = engine.hf_solve(net.mlp, net.params, data.x, data.y, n_global=data.n_global,
@@ -379,7 +387,7 @@ class UnifiedOWLQN(UnifiedOptimizer):
 
     def optimize(self, net, data, config):
         if config.eval_every > 0:
-            raise LbfError("UnifiedOWLQN has no resumable form: eval_every > 0 needs UnifiedLBFGS or UnifiedSLBFGS")
+            raise LbfError("UnifiedOWLQN has no resumable form: eval_every > 0 needs UnifiedLBFGS, UnifiedSLBFGS or UnifiedAdam")
         hist, info, stats = engine.owlqn_solve(net.mlp, net.params, data.x, data.y, n_global=data.n_global,
                                                m=config.m_param, max_iters=config.max_iters, tol=config.tolerance,
                                                l1=config.l1)
@@ -399,7 +407,7 @@ class UnifiedSGD(UnifiedOptimizer):
 
     def optimize(self, net, data, config):
         if config.eval_every > 0:
-            raise LbfError("UnifiedSGD has no resumable form: eval_every > 0 needs UnifiedLBFGS or UnifiedSLBFGS")
+            raise LbfError("UnifiedSGD has no resumable form: eval_every > 0 needs UnifiedLBFGS, UnifiedSLBFGS or UnifiedAdam")
         hist, info = engine.sgd_solve(net.mlp, net.params, data.x_full, data.y_full, lr=config.learning_rate,
                                       momentum=config.momentum, batch=config.batch_size, max_epochs=config.max_iters,
                                       decay_rate=config.lr_decay, decay_step=config.lr_decay_rate)
@@ -408,6 +416,40 @@ class UnifiedSGD(UnifiedOptimizer):
             rec.record(i, float(hist["loss"][i]), float(hist["grad_norm"][i]), float(hist["time_ms"][i]))
         self.info = info
         self.history = hist
+        return rec
+
+
+class UnifiedAdam(UnifiedOptimizer):
+    """Adam / AdamW over shuffled minibatches (HIP extension, no reference counterpart): engine.adam_solve with the
+    config's learning_rate, beta1, beta2, adam_eps, weight_decay, clip_norm, batch_size, shuffle, seed and max_iters
+    epochs; lr_decay / lr_decay_rate as UnifiedSGD reads them, but only when lr_decay > 0. The loss and l2 are the
+    network's; the stopping tolerance stays the solver's 1e-6, as for UnifiedSGD. Every rank holds all rows and takes
+    its slice of every batch. config.eval_every > 0: the same solve through AdamRun, an epoch per iteration, with
+    validation, early stopping and restore_best (_monitored_run). The batch objectives are kept in self.trace."""
+
+    @staticmethod
+    def _kw(config):
+        decay = config.lr_decay > 0
+        return dict(lr=config.learning_rate, beta1=config.beta1, beta2=config.beta2, eps=config.adam_eps,
+                    weight_decay=config.weight_decay, clip_norm=config.clip_norm, batch=config.batch_size,
+                    shuffle=config.shuffle, seed=config.seed, max_epochs=config.max_iters,
+                    decay_rate=config.lr_decay if decay else 1.0, decay_step=config.lr_decay_rate if decay else 0)
+
+    def optimize(self, net, data, config):
+        if config.eval_every > 0:
+            _check_monitored(config, data)
+            run = engine.AdamRun(net.mlp, net.params, data.x_full, data.y_full,
+                                 record_cap=max(config.max_iters, 1) + 1, **self._kw(config))
+            rec = _monitored_run(self, net, data, config, run)
+            self.trace = run.loss_trace()
+            return rec
+        hist, info, trace = engine.adam_solve(net.mlp, net.params, data.x_full, data.y_full, **self._kw(config))
+        rec = IterationRecorder()
+        for i in range(len(hist["loss"])):
+            rec.record(i, float(hist["loss"][i]), float(hist["grad_norm"][i]), float(hist["time_ms"][i]))
+        self.info = info
+        self.history = hist
+        self.trace = trace
         return rec
 
 
