@@ -230,34 +230,6 @@ private:
   DeviceBuffer<HipScalar> params_, grads_;
 };
 
-/// Abstract minimizer (CudaMinimizerBase, src/cuda/minimizer_base.cuh:12-67).
-class HipMinimizerBase {
-public:
-  using LossGradFun = std::function<HipScalar(const HipScalar *params, HipScalar *grad, const HipScalar *input,
-                                              const HipScalar *target, int batch)>;
-  using IterHook = std::function<void(int)>;
-  explicit HipMinimizerBase(HipHandle &handle) : handle_(handle) {}
-  virtual ~HipMinimizerBase() = default;
-  int iterations() const noexcept { return last_iterations_; }
-  void setRecorder(::IterationRecorder<HipBackend> *recorder) { recorder_ = recorder; }
-  void setMaxIterations(int iters) { max_iters_ = iters; }
-  void setTolerance(HipScalar tol) { tol_ = tol; }
-  void setLineSearchParams(int max_iters, HipScalar c1, HipScalar rho) {
-    max_line_iters_ = (max_iters < 1) ? 1 : max_iters;
-    c1_ = c1;
-    rho_ = rho;
-  }
-  virtual void solve(int n, HipScalar *params, const HipScalar *input, const HipScalar *target, int batch,
-                     const LossGradFun &loss_grad) = 0;
-
-protected:
-  HipHandle &handle_;
-  int max_iters_ = 200, max_line_iters_ = 20;
-  HipScalar tol_ = 1e-6f, c1_ = 1e-4f, rho_ = 0.5f;
-  int last_iterations_ = 0;
-  ::IterationRecorder<HipBackend> *recorder_ = nullptr;
-};
-
 } // namespace hip_mlp
 
 /// Host-side history of (loss, ||g||, cumulative ms) per iteration (iteration_recorder.hpp:13-146;
@@ -308,6 +280,50 @@ private:
 
 namespace hip_mlp {
 
+/// Abstract minimizer (CudaMinimizerBase, src/cuda/minimizer_base.cuh:12-67).
+class HipMinimizerBase {
+public:
+  using LossGradFun = std::function<HipScalar(const HipScalar *params, HipScalar *grad, const HipScalar *input,
+                                              const HipScalar *target, int batch)>;
+  using IterHook = std::function<void(int)>;
+  explicit HipMinimizerBase(HipHandle &handle) : handle_(handle) {}
+  virtual ~HipMinimizerBase() = default;
+  int iterations() const noexcept { return last_iterations_; }
+  void setRecorder(::IterationRecorder<HipBackend> *recorder) { recorder_ = recorder; }
+  void setMaxIterations(int iters) { max_iters_ = iters; }
+  void setTolerance(HipScalar tol) { tol_ = tol; }
+  void setLineSearchParams(int max_iters, HipScalar c1, HipScalar rho) {
+    max_line_iters_ = (max_iters < 1) ? 1 : max_iters;
+    c1_ = c1;
+    rho_ = rho;
+  }
+  virtual void solve(int n, HipScalar *params, const HipScalar *input, const HipScalar *target, int batch,
+                     const LossGradFun &loss_grad) = 0;
+
+protected:
+  /// What every solve() shares. Nothing to solve (lbfgs.cuh:45-48): zero iterations and no engine call. Otherwise
+  /// call(rec, info) runs the entry point, rec being the recorder's arrays (null without a recorder).
+  template <class Call> void run(int n, const HipScalar *params, const char *what, Call &&call) {
+    last_iterations_ = 0;
+    if (n <= 0 || params == nullptr) return;
+    lbf_record rec{};
+    if (recorder_) {
+      recorder_->reset();
+      rec = recorder_->view();
+    }
+    lbf_solve_info info{};
+    hip_check(call(recorder_ ? &rec : nullptr, &info), what);
+    if (recorder_) recorder_->set_size(rec.size);
+    last_iterations_ = info.iterations;
+  }
+
+  HipHandle &handle_;
+  int max_iters_ = 200, max_line_iters_ = 20;
+  HipScalar tol_ = 1e-6f, c1_ = 1e-4f, rho_ = 0.5f;
+  int last_iterations_ = 0;
+  ::IterationRecorder<HipBackend> *recorder_ = nullptr;
+};
+
 /// L-BFGS with the reference's CUDA semantics by default (Armijo + interpolation, lbfgs.cuh:39-194);
 /// setLineSearch(LBF_LS_WOLFE) selects the CPU semantics (lbfgs.hpp:38-100). Any LossGradFun works:
 /// the engine keeps the (s, y) history, two-loop and line search on the device.
@@ -319,10 +335,6 @@ public:
 
   void solve(int n, HipScalar *params, const HipScalar *input, const HipScalar *target, int batch,
              const LossGradFun &loss_grad) override {
-    if (n <= 0 || params == nullptr) { // lbfgs.cuh:45-48
-      last_iterations_ = 0;
-      return;
-    }
     struct Closure {
       const LossGradFun *f;
       const HipScalar *in, *tg;
@@ -342,17 +354,9 @@ public:
       prm.c1 = c1_;
       prm.rho = rho_;
     }
-    lbf_record rec{};
-    lbf_record *rp = nullptr;
-    if (recorder_) {
-      recorder_->reset();
-      rec = recorder_->view();
-      rp = &rec;
-    }
-    lbf_solve_info info{};
-    hip_check(lbf_lbfgs_solve_fn(handle_.get(), &prm, n, params, tramp, &cl, rp, &info), "lbf_lbfgs_solve_fn");
-    if (recorder_) recorder_->set_size(rec.size);
-    last_iterations_ = info.iterations;
+    run(n, params, "lbf_lbfgs_solve_fn", [&](lbf_record *rec, lbf_solve_info *info) {
+      return lbf_lbfgs_solve_fn(handle_.get(), &prm, n, params, tramp, &cl, rec, info);
+    });
   }
 
 private:
@@ -360,13 +364,9 @@ private:
   int ls_ = LBF_LS_ARMIJO;
 };
 
-/// Hessian-free (truncated Newton) minimizer on a HipNetwork (HIP extension, no reference counterpart:
-/// lbf_hf_solve, Gauss-Newton CG steps with Levenberg-Marquardt damping). The curvature needs the network, not
-/// only its loss and gradient, so solve() minimises the network's own loss (+ its l2) on input / target and does
-/// not call loss_grad; n must be the network's parameter count.
-class HipHF : public HipMinimizerBase {
+/// What HipHF and HipHFPreconditioned share: the network, the setters and the lbf_hf_params they give.
+class HipHFBase : public HipMinimizerBase {
 public:
-  HipHF(HipHandle &handle, HipNetwork &net) : HipMinimizerBase(handle), net_(net) {}
   void setCG(int iters, double rtol) {
     cg_iters_ = iters;
     cg_rtol_ = rtol;
@@ -374,12 +374,9 @@ public:
   void setDamping(double damping0) { damping0_ = damping0; }
   void setCurvatureRows(long long rows) { curv_rows_ = rows; }
 
-  void solve(int n, HipScalar *params, const HipScalar *input, const HipScalar *target, int batch,
-             const LossGradFun &) override {
-    if (n <= 0 || params == nullptr) {
-      last_iterations_ = 0;
-      return;
-    }
+protected:
+  HipHFBase(HipHandle &handle, HipNetwork &net) : HipMinimizerBase(handle), net_(net) {}
+  lbf_hf_params hfParams() const {
     lbf_hf_params prm;
     lbf_hf_default_params(&prm);
     prm.max_iters = max_iters_;
@@ -391,86 +388,61 @@ public:
     prm.max_line_iters = max_line_iters_;
     prm.c1 = c1_;
     prm.rho = rho_;
-    lbf_record rec{};
-    lbf_record *rp = nullptr;
-    if (recorder_) {
-      recorder_->reset();
-      rec = recorder_->view();
-      rp = &rec;
-    }
-    lbf_solve_info info{};
-    hip_check(lbf_hf_solve(net_.raw(), &prm, params, input, target, batch, batch, rp, &info), "lbf_hf_solve");
-    if (recorder_) recorder_->set_size(rec.size);
-    last_iterations_ = info.iterations;
+    return prm;
   }
+  HipNetwork &net_;
 
 private:
-  HipNetwork &net_;
   int cg_iters_ = 50;
   double cg_rtol_ = 0.1, damping0_ = 1.0;
   long long curv_rows_ = 0;
 };
 
+/// Hessian-free (truncated Newton) minimizer on a HipNetwork (HIP extension, no reference counterpart:
+/// lbf_hf_solve, Gauss-Newton CG steps with Levenberg-Marquardt damping). The curvature needs the network, not
+/// only its loss and gradient, so solve() minimises the network's own loss (+ its l2) on input / target and does
+/// not call loss_grad; n must be the network's parameter count.
+class HipHF : public HipHFBase {
+public:
+  HipHF(HipHandle &handle, HipNetwork &net) : HipHFBase(handle, net) {}
+  void solve(int n, HipScalar *params, const HipScalar *input, const HipScalar *target, int batch,
+             const LossGradFun &) override {
+    const lbf_hf_params prm = hfParams();
+    run(n, params, "lbf_hf_solve", [&](lbf_record *rec, lbf_solve_info *info) {
+      return lbf_hf_solve(net_.raw(), &prm, params, input, target, batch, batch, rec, info);
+    });
+  }
+};
+
 /// HipHF with the CG preconditioned by the squared-gradient diagonal (lbf_hf_solve_pc, LBF_PRECOND_GRAD_SQ):
 /// M = (D / rows + l2 + damping)^exponent, D = HipNetwork::gradSq of the curvature rows. A class of its own, so that
 /// a program using HipHF alone links against a library that predates lbf_hf_solve_pc.
-class HipHFPreconditioned : public HipMinimizerBase {
+class HipHFPreconditioned : public HipHFBase {
 public:
-  HipHFPreconditioned(HipHandle &handle, HipNetwork &net) : HipMinimizerBase(handle), net_(net) {}
-  void setCG(int iters, double rtol) {
-    cg_iters_ = iters;
-    cg_rtol_ = rtol;
-  }
-  void setDamping(double damping0) { damping0_ = damping0; }
-  void setCurvatureRows(long long rows) { curv_rows_ = rows; }
+  HipHFPreconditioned(HipHandle &handle, HipNetwork &net) : HipHFBase(handle, net) {}
   /// exponent in [0, 1] (0: no preconditioning, the bits of HipHF); refresh: outer iterations between two
   /// evaluations of D
-  void setPreconditioner(double exponent, int refresh = 1) {
-    exponent_ = exponent;
-    refresh_ = refresh;
+  void setPreconditioner(double exponent, int refresh = 1) { pc_ = gradSqPreconditioner(exponent, refresh); }
+  /// the lbf_hf_precond of this class and of UnifiedHFPreconditioned_HIP
+  static lbf_hf_precond gradSqPreconditioner(double exponent, int refresh) {
+    lbf_hf_precond pc;
+    lbf_hf_precond_default(&pc);
+    pc.mode = LBF_PRECOND_GRAD_SQ;
+    pc.exponent = exponent;
+    pc.refresh = refresh;
+    return pc;
   }
 
   void solve(int n, HipScalar *params, const HipScalar *input, const HipScalar *target, int batch,
              const LossGradFun &) override {
-    if (n <= 0 || params == nullptr) {
-      last_iterations_ = 0;
-      return;
-    }
-    lbf_hf_params prm;
-    lbf_hf_default_params(&prm);
-    prm.max_iters = max_iters_;
-    prm.tol = tol_;
-    prm.cg_iters = cg_iters_;
-    prm.cg_rtol = cg_rtol_;
-    prm.damping0 = damping0_;
-    prm.curv_rows = curv_rows_;
-    prm.max_line_iters = max_line_iters_;
-    prm.c1 = c1_;
-    prm.rho = rho_;
-    lbf_hf_precond pc;
-    lbf_hf_precond_default(&pc);
-    pc.mode = LBF_PRECOND_GRAD_SQ;
-    pc.exponent = exponent_;
-    pc.refresh = refresh_;
-    lbf_record rec{};
-    lbf_record *rp = nullptr;
-    if (recorder_) {
-      recorder_->reset();
-      rec = recorder_->view();
-      rp = &rec;
-    }
-    lbf_solve_info info{};
-    hip_check(lbf_hf_solve_pc(net_.raw(), &prm, &pc, params, input, target, batch, batch, rp, &info),
-              "lbf_hf_solve_pc");
-    if (recorder_) recorder_->set_size(rec.size);
-    last_iterations_ = info.iterations;
+    const lbf_hf_params prm = hfParams();
+    run(n, params, "lbf_hf_solve_pc", [&](lbf_record *rec, lbf_solve_info *info) {
+      return lbf_hf_solve_pc(net_.raw(), &prm, &pc_, params, input, target, batch, batch, rec, info);
+    });
   }
 
 private:
-  HipNetwork &net_;
-  int cg_iters_ = 50, refresh_ = 1;
-  double cg_rtol_ = 0.1, damping0_ = 1.0, exponent_ = 0.75;
-  long long curv_rows_ = 0;
+  lbf_hf_precond pc_ = gradSqPreconditioner(0.75, 1);
 };
 
 /// OWL-QN minimizer on a HipNetwork (HIP extension, no reference counterpart: lbf_owlqn_solve, L-BFGS on the
@@ -490,10 +462,6 @@ public:
 
   void solve(int n, HipScalar *params, const HipScalar *input, const HipScalar *target, int batch,
              const LossGradFun &) override {
-    if (n <= 0 || params == nullptr) {
-      last_iterations_ = 0;
-      return;
-    }
     lbf_owlqn_params prm;
     lbf_owlqn_default_params(&prm);
     prm.m = m_;
@@ -504,18 +472,9 @@ public:
     prm.max_line_iters = max_line_iters_;
     prm.c1 = c1_;
     prm.rho = rho_;
-    lbf_record rec{};
-    lbf_record *rp = nullptr;
-    if (recorder_) {
-      recorder_->reset();
-      rec = recorder_->view();
-      rp = &rec;
-    }
-    lbf_solve_info info{};
-    hip_check(lbf_owlqn_solve(net_.raw(), &prm, params, input, target, batch, batch, rp, &info, &stats_),
-              "lbf_owlqn_solve");
-    if (recorder_) recorder_->set_size(rec.size);
-    last_iterations_ = info.iterations;
+    run(n, params, "lbf_owlqn_solve", [&](lbf_record *rec, lbf_solve_info *info) {
+      return lbf_owlqn_solve(net_.raw(), &prm, params, input, target, batch, batch, rec, info, &stats_);
+    });
   }
 
 private:
@@ -524,6 +483,19 @@ private:
   int l1_bias_ = 0, m_ = 10;
   lbf_owlqn_stats stats_{};
 };
+
+/// Adam's loss trace, for HipAdam and UnifiedAdam_HIP: one entry per step, ceil(rows / batch) steps in each of
+/// prm.max_epochs epochs, NaN until the step has run. Sizes `trace` and points prm at it (no steps: a null pointer).
+inline void adam_trace_attach(std::vector<double> &trace, lbf_adam_params &prm, long long rows) {
+  const long long per_epoch = prm.batch > 0 ? (rows + prm.batch - 1) / prm.batch : 0;
+  trace.assign(size_t(std::max(0LL, per_epoch * std::max(0, prm.max_epochs))), std::nan(""));
+  prm.loss_trace = trace.empty() ? nullptr : trace.data();
+  prm.trace_cap = int(trace.size());
+}
+/// After the solve: drops the steps that did not run.
+inline void adam_trace_trim(std::vector<double> &trace) {
+  while (!trace.empty() && std::isnan(trace.back())) trace.pop_back();
+}
 
 /// Adam / AdamW minimizer on a HipNetwork (HIP extension, no reference counterpart: lbf_adam_solve, shuffled
 /// minibatches, one fused evaluation and one device-side sweep per step). Like HipHF, solve() minimises the
@@ -555,29 +527,14 @@ public:
 
   void solve(int n, HipScalar *params, const HipScalar *input, const HipScalar *target, int batch,
              const LossGradFun &) override {
-    if (n <= 0 || params == nullptr) {
-      last_iterations_ = 0;
-      return;
-    }
-    lbf_adam_params prm = prm_;
-    prm.max_epochs = max_iters_;
-    prm.tol = tol_;
-    const long long per_epoch = prm.batch > 0 ? (static_cast<long long>(batch) + prm.batch - 1) / prm.batch : 0;
-    trace_.assign(size_t(std::max(0LL, per_epoch * std::max(0, max_iters_))), std::nan(""));
-    prm.loss_trace = trace_.empty() ? nullptr : trace_.data();
-    prm.trace_cap = int(trace_.size());
-    lbf_record rec{};
-    lbf_record *rp = nullptr;
-    if (recorder_) {
-      recorder_->reset();
-      rec = recorder_->view();
-      rp = &rec;
-    }
-    lbf_solve_info info{};
-    hip_check(lbf_adam_solve(net_.raw(), &prm, params, input, target, batch, rp, &info), "lbf_adam_solve");
-    if (recorder_) recorder_->set_size(rec.size);
-    last_iterations_ = info.iterations;
-    while (!trace_.empty() && std::isnan(trace_.back())) trace_.pop_back(); // the steps that did not run
+    run(n, params, "lbf_adam_solve", [&](lbf_record *rec, lbf_solve_info *info) {
+      lbf_adam_params prm = prm_;
+      prm.max_epochs = max_iters_;
+      prm.tol = tol_;
+      adam_trace_attach(trace_, prm, batch);
+      return lbf_adam_solve(net_.raw(), &prm, params, input, target, batch, rec, info);
+    });
+    adam_trace_trim(trace_);
   }
 
 private:
@@ -717,7 +674,36 @@ public:
                         hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &d_train_y, const UnifiedConfig &config) = 0;
   IterationRecorder<HipBackend> recorder;
   int line_search = LBF_LS_ARMIJO; // UnifiedLBFGS_CUDA's semantics unless set to LBF_LS_WOLFE
+
+protected:
+  /// What every optimize() shares: a record of `cap` rows, call(network, n_train, rec, info) runs the entry point,
+  /// then the recorder's size and the history CSV.
+  template <class Call>
+  void run(NetworkWrapper<HipBackend> &net, const UnifiedDataset &host_data, const UnifiedConfig &c, int cap,
+           const char *what, Call &&call) {
+    recorder.init(cap);
+    lbf_record rec = recorder.view();
+    lbf_solve_info info{};
+    hip_mlp::hip_check(call(net.getInternal(), long(host_data.train_x.cols()), &rec, &info), what);
+    recorder.set_size(rec.size);
+    write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
+  }
 };
+
+/// lbf_hf_params of UnifiedHF_HIP and UnifiedHFPreconditioned_HIP: the config's max_iters and tolerance and, where
+/// the config is this header's own, its cg_iters, cg_rtol and damping.
+inline lbf_hf_params hip_hf_params(const UnifiedConfig &c) {
+  lbf_hf_params prm;
+  lbf_hf_default_params(&prm);
+  prm.max_iters = c.max_iters;
+  prm.tol = c.tolerance;
+#ifndef LBF_USE_REFERENCE_UNIFIED_TYPES // the reference's own UnifiedConfig has no such members
+  prm.cg_iters = c.cg_iters;
+  prm.cg_rtol = c.cg_rtol;
+  prm.damping0 = c.damping;
+#endif
+  return prm;
+}
 
 /// UnifiedLBFGS_CUDA counterpart (unified_optimization.hpp:560-592): full-batch L-BFGS of the MLP,
 /// all on the device (no per-evaluation callback or D2D gradient copy, cf. :483-491).
@@ -726,21 +712,15 @@ public:
   void optimize(hip_mlp::HipHandle &, NetworkWrapper<HipBackend> &net, const UnifiedDataset &host_data,
                 hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dx, hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dy,
                 const UnifiedConfig &c) override {
-    const long n_train = long(host_data.train_x.cols());
-    auto &nw = net.getInternal();
     lbf_lbfgs_params prm;
     lbf_lbfgs_default_params(&prm, line_search);
     prm.m = c.m_param > 0 ? c.m_param : 10;
     prm.max_iters = c.max_iters;
     prm.tol = c.tolerance;
-    recorder.init(c.max_iters);
-    lbf_record rec = recorder.view();
-    lbf_solve_info info{};
-    hip_mlp::hip_check(lbf_lbfgs_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n_train, n_train,
-                                       &rec, &info),
-                       "lbf_lbfgs_solve");
-    recorder.set_size(rec.size);
-    write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
+    run(net, host_data, c, c.max_iters, "lbf_lbfgs_solve",
+        [&](hip_mlp::HipNetwork &nw, long n, lbf_record *rec, lbf_solve_info *info) {
+          return lbf_lbfgs_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n, n, rec, info);
+        });
   }
 };
 
@@ -750,8 +730,6 @@ public:
   void optimize(hip_mlp::HipHandle &, NetworkWrapper<HipBackend> &net, const UnifiedDataset &host_data,
                 hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dx, hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dy,
                 const UnifiedConfig &c) override {
-    const long n_train = long(host_data.train_x.cols());
-    auto &nw = net.getInternal();
     lbf_slbfgs_params prm;
     lbf_slbfgs_default_params(&prm);
     prm.max_epochs = c.max_iters;
@@ -764,13 +742,10 @@ public:
 #ifndef LBF_USE_REFERENCE_UNIFIED_TYPES // the reference's own UnifiedConfig has no such member
     prm.hvp_exact = c.curvature;
 #endif
-    recorder.init(c.max_iters);
-    lbf_record rec = recorder.view();
-    lbf_solve_info info{};
-    hip_mlp::hip_check(lbf_slbfgs_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n_train, &rec, &info),
-                       "lbf_slbfgs_solve");
-    recorder.set_size(rec.size);
-    write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
+    run(net, host_data, c, c.max_iters, "lbf_slbfgs_solve",
+        [&](hip_mlp::HipNetwork &nw, long n, lbf_record *rec, lbf_solve_info *info) {
+          return lbf_slbfgs_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n, rec, info);
+        });
   }
 };
 
@@ -781,51 +756,30 @@ public:
   void optimize(hip_mlp::HipHandle &, NetworkWrapper<HipBackend> &net, const UnifiedDataset &host_data,
                 hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dx, hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dy,
                 const UnifiedConfig &c) override {
-    const long n_train = long(host_data.train_x.cols());
-    auto &nw = net.getInternal();
     lbf_gd_params prm;
     lbf_gd_default_params(&prm);
     prm.lr = c.learning_rate;
     prm.momentum = c.momentum;
     prm.max_iters = c.max_iters;
     prm.tol = c.tolerance;
-    recorder.init(c.max_iters);
-    lbf_record rec = recorder.view();
-    lbf_solve_info info{};
-    hip_mlp::hip_check(lbf_gd_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n_train, n_train, &rec,
-                                    &info),
-                       "lbf_gd_solve");
-    recorder.set_size(rec.size);
-    write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
+    run(net, host_data, c, c.max_iters, "lbf_gd_solve",
+        [&](hip_mlp::HipNetwork &nw, long n, lbf_record *rec, lbf_solve_info *info) {
+          return lbf_gd_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n, n, rec, info);
+        });
   }
 };
 
-/// Hessian-free training (HIP extension, no reference counterpart): lbf_hf_solve with the config's max_iters and
-/// tolerance and, where the config is this header's own, its cg_iters, cg_rtol and damping.
+/// Hessian-free training (HIP extension, no reference counterpart): lbf_hf_solve with hip_hf_params(config).
 class UnifiedHF_HIP : public UnifiedOptimizer<HipBackend> {
 public:
   void optimize(hip_mlp::HipHandle &, NetworkWrapper<HipBackend> &net, const UnifiedDataset &host_data,
                 hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dx, hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dy,
                 const UnifiedConfig &c) override {
-    const long n_train = long(host_data.train_x.cols());
-    auto &nw = net.getInternal();
-    lbf_hf_params prm;
-    lbf_hf_default_params(&prm);
-    prm.max_iters = c.max_iters;
-    prm.tol = c.tolerance;
-#ifndef LBF_USE_REFERENCE_UNIFIED_TYPES // the reference's own UnifiedConfig has no such members
-    prm.cg_iters = c.cg_iters;
-    prm.cg_rtol = c.cg_rtol;
-    prm.damping0 = c.damping;
-#endif
-    recorder.init(c.max_iters);
-    lbf_record rec = recorder.view();
-    lbf_solve_info info{};
-    hip_mlp::hip_check(lbf_hf_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n_train, n_train, &rec,
-                                    &info),
-                       "lbf_hf_solve");
-    recorder.set_size(rec.size);
-    write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
+    const lbf_hf_params prm = hip_hf_params(c);
+    run(net, host_data, c, c.max_iters, "lbf_hf_solve",
+        [&](hip_mlp::HipNetwork &nw, long n, lbf_record *rec, lbf_solve_info *info) {
+          return lbf_hf_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n, n, rec, info);
+        });
   }
 };
 
@@ -835,41 +789,20 @@ public:
 class UnifiedHFPreconditioned_HIP : public UnifiedOptimizer<HipBackend> {
 public:
   void setPreconditioner(double exponent, int refresh = 1) {
-    exponent_ = exponent;
-    refresh_ = refresh;
+    pc_ = hip_mlp::HipHFPreconditioned::gradSqPreconditioner(exponent, refresh);
   }
   void optimize(hip_mlp::HipHandle &, NetworkWrapper<HipBackend> &net, const UnifiedDataset &host_data,
                 hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dx, hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dy,
                 const UnifiedConfig &c) override {
-    const long n_train = long(host_data.train_x.cols());
-    auto &nw = net.getInternal();
-    lbf_hf_params prm;
-    lbf_hf_default_params(&prm);
-    prm.max_iters = c.max_iters;
-    prm.tol = c.tolerance;
-#ifndef LBF_USE_REFERENCE_UNIFIED_TYPES // the reference's own UnifiedConfig has no such members
-    prm.cg_iters = c.cg_iters;
-    prm.cg_rtol = c.cg_rtol;
-    prm.damping0 = c.damping;
-#endif
-    lbf_hf_precond pc;
-    lbf_hf_precond_default(&pc);
-    pc.mode = LBF_PRECOND_GRAD_SQ;
-    pc.exponent = exponent_;
-    pc.refresh = refresh_;
-    recorder.init(c.max_iters);
-    lbf_record rec = recorder.view();
-    lbf_solve_info info{};
-    hip_mlp::hip_check(lbf_hf_solve_pc(nw.raw(), &prm, &pc, nw.params_data(), dx.data(), dy.data(), n_train, n_train,
-                                       &rec, &info),
-                       "lbf_hf_solve_pc");
-    recorder.set_size(rec.size);
-    write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
+    const lbf_hf_params prm = hip_hf_params(c);
+    run(net, host_data, c, c.max_iters, "lbf_hf_solve_pc",
+        [&](hip_mlp::HipNetwork &nw, long n, lbf_record *rec, lbf_solve_info *info) {
+          return lbf_hf_solve_pc(nw.raw(), &prm, &pc_, nw.params_data(), dx.data(), dy.data(), n, n, rec, info);
+        });
   }
 
 private:
-  double exponent_ = 0.75;
-  int refresh_ = 1;
+  lbf_hf_precond pc_ = hip_mlp::HipHFPreconditioned::gradSqPreconditioner(0.75, 1);
 };
 
 /// L1-regularised L-BFGS (HIP extension, no reference counterpart): lbf_owlqn_solve with the config's m_param,
@@ -880,8 +813,6 @@ public:
   void optimize(hip_mlp::HipHandle &, NetworkWrapper<HipBackend> &net, const UnifiedDataset &host_data,
                 hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dx, hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dy,
                 const UnifiedConfig &c) override {
-    const long n_train = long(host_data.train_x.cols());
-    auto &nw = net.getInternal();
     lbf_owlqn_params prm;
     lbf_owlqn_default_params(&prm);
     prm.m = c.m_param;
@@ -890,14 +821,10 @@ public:
 #ifndef LBF_USE_REFERENCE_UNIFIED_TYPES // the reference's own UnifiedConfig has no such member
     prm.l1 = c.l1;
 #endif
-    recorder.init(c.max_iters);
-    lbf_record rec = recorder.view();
-    lbf_solve_info info{};
-    hip_mlp::hip_check(lbf_owlqn_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n_train, n_train,
-                                       &rec, &info, &stats),
-                       "lbf_owlqn_solve");
-    recorder.set_size(rec.size);
-    write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
+    run(net, host_data, c, c.max_iters, "lbf_owlqn_solve",
+        [&](hip_mlp::HipNetwork &nw, long n, lbf_record *rec, lbf_solve_info *info) {
+          return lbf_owlqn_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n, n, rec, info, &stats);
+        });
   }
 };
 
@@ -911,8 +838,6 @@ public:
   void optimize(hip_mlp::HipHandle &, NetworkWrapper<HipBackend> &net, const UnifiedDataset &host_data,
                 hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dx, hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dy,
                 const UnifiedConfig &c) override {
-    const long n_train = long(host_data.train_x.cols());
-    auto &nw = net.getInternal();
     lbf_adam_params prm;
     lbf_adam_default_params(&prm);
     prm.lr = c.learning_rate;
@@ -931,18 +856,12 @@ public:
     prm.clip_norm = c.clip_norm;
     prm.shuffle = c.shuffle ? 1 : 0;
 #endif
-    const long long per_epoch = prm.batch > 0 ? (static_cast<long long>(n_train) + prm.batch - 1) / prm.batch : 0;
-    trace.assign(size_t(std::max(0LL, per_epoch * std::max(0, c.max_iters))), std::nan(""));
-    prm.loss_trace = trace.empty() ? nullptr : trace.data();
-    prm.trace_cap = int(trace.size());
-    recorder.init(c.max_iters + 1);
-    lbf_record rec = recorder.view();
-    lbf_solve_info info{};
-    hip_mlp::hip_check(lbf_adam_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n_train, &rec, &info),
-                       "lbf_adam_solve");
-    recorder.set_size(rec.size);
-    while (!trace.empty() && std::isnan(trace.back())) trace.pop_back(); // the steps that did not run
-    write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
+    run(net, host_data, c, c.max_iters + 1, "lbf_adam_solve",
+        [&](hip_mlp::HipNetwork &nw, long n, lbf_record *rec, lbf_solve_info *info) {
+          hip_mlp::adam_trace_attach(trace, prm, n);
+          return lbf_adam_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n, rec, info);
+        });
+    hip_mlp::adam_trace_trim(trace);
   }
 };
 
@@ -954,8 +873,6 @@ public:
   void optimize(hip_mlp::HipHandle &, NetworkWrapper<HipBackend> &net, const UnifiedDataset &host_data,
                 hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dx, hip_mlp::DeviceBuffer<hip_mlp::HipScalar> &dy,
                 const UnifiedConfig &c) override {
-    const long n_train = long(host_data.train_x.cols());
-    auto &nw = net.getInternal();
     lbf_sgd_params prm;
     lbf_sgd_default_params(&prm);
     prm.lr = c.learning_rate;
@@ -964,13 +881,10 @@ public:
     prm.max_epochs = c.max_iters;
     prm.decay_rate = c.lr_decay;
     prm.decay_step = c.lr_decay_rate;
-    recorder.init(c.max_iters + 1);
-    lbf_record rec = recorder.view();
-    lbf_solve_info info{};
-    hip_mlp::hip_check(lbf_sgd_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n_train, &rec, &info),
-                       "lbf_sgd_solve");
-    recorder.set_size(rec.size);
-    write_hip_history_csv(hip_log_filename(c), recorder, c.log_interval);
+    run(net, host_data, c, c.max_iters + 1, "lbf_sgd_solve",
+        [&](hip_mlp::HipNetwork &nw, long n, lbf_record *rec, lbf_solve_info *info) {
+          return lbf_sgd_solve(nw.raw(), &prm, nw.params_data(), dx.data(), dy.data(), n, rec, info);
+        });
   }
 };
 

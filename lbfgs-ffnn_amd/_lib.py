@@ -114,6 +114,112 @@ class EvalResultC(C.Structure):  # lbf_eval_result
 _lib = None
 _vp, _ip, _dp, _fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_float)
 
+# (restype, argtypes) of every function include/lbfgs_amd.h declares: the one place a new entry point is named
+_SIG = {
+    "lbf_last_error": (C.c_char_p, []),
+    "lbf_version": (C.c_char_p, []),
+    "lbf_abi_version": (C.c_int, []),
+    "lbf_ctx_create": (C.c_int, [C.c_int, _vp, C.POINTER(_vp)]),
+    "lbf_ctx_destroy": (C.c_int, [_vp]),
+    "lbf_ctx_sync": (C.c_int, [_vp]),
+    "lbf_ctx_stream": (_vp, [_vp]),
+    "lbf_comm_unique_id": (C.c_int, [C.c_char_p]),
+    "lbf_comm_init": (C.c_int, [_vp, C.c_int, C.c_int, C.c_char_p]),
+    "lbf_comm_init_local": (C.c_int, [C.POINTER(_vp), C.c_int]),
+    "lbf_comm_rank": (C.c_int, [_vp, _ip, _ip]),
+    "lbf_allreduce_sum": (C.c_int, [_vp, _vp, C.c_size_t]),
+    "lbf_mlp_create": (C.c_int, [_vp, C.c_int, _ip, _ip, C.POINTER(_vp)]),
+    "lbf_mlp_destroy": (C.c_int, [_vp]),
+    "lbf_mlp_param_count": (C.c_longlong, [_vp]),
+    "lbf_mlp_init_params": (C.c_int, [_vp, C.c_uint, C.c_int, _vp]),
+    "lbf_init_params_host": (C.c_int, [C.c_int, _ip, _ip, C.c_uint, C.c_int, _vp]),
+    "lbf_mlp_forward": (C.c_int, [_vp, _vp, _vp, C.c_longlong, _vp]),
+    "lbf_mlp_loss_grad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_double, _dp]),
+    "lbf_mlp_batch_grads": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_longlong, C.c_double, C.c_double, _vp,
+                                      C.c_longlong]),
+    "lbf_two_loop": (C.c_int, [_vp, C.c_longlong, C.c_int, _vp, _vp, _dp, _vp, _vp, C.c_int]),
+    "lbf_dot": (C.c_int, [_vp, C.c_longlong, _vp, _vp, _dp]),
+    "lbf_nrm2": (C.c_int, [_vp, C.c_longlong, _vp, _dp]),
+    "lbf_axpy": (C.c_int, [_vp, C.c_longlong, C.c_float, _vp, _vp]),
+    "lbf_scal": (C.c_int, [_vp, C.c_longlong, C.c_float, _vp]),
+    "lbf_lbfgs_default_params": (None, [C.POINTER(LbfgsParams), C.c_int]),
+    "lbf_slbfgs_default_params": (None, [C.POINTER(SlbfgsParams)]),
+    "lbf_lbfgs_solve": (C.c_int, [_vp, C.POINTER(LbfgsParams), _vp, _vp, _vp, C.c_longlong, C.c_longlong,
+                                  C.POINTER(Record), C.POINTER(SolveInfo)]),
+    "lbf_lbfgs_begin": (C.c_int, [_vp, C.POINTER(LbfgsParams), _vp, _vp, _vp, C.c_longlong, C.c_longlong,
+                                  C.POINTER(_vp)]),
+    "lbf_lbfgs_iterate": (C.c_int, [_vp, C.c_int, C.POINTER(Record), C.POINTER(SolveInfo)]),
+    "lbf_lbfgs_end": (C.c_int, [_vp]),
+    "lbf_lbfgs_solve_fn": (C.c_int, [_vp, C.POINTER(LbfgsParams), C.c_longlong, _vp, _vp, _vp,
+                                     C.POINTER(Record), C.POINTER(SolveInfo)]),
+    "lbf_device_alloc": (C.c_int, [_vp, C.c_size_t, C.POINTER(_vp)]),
+    "lbf_device_free": (C.c_int, [_vp, _vp]),
+    "lbf_memcpy": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int]),
+    "lbf_slbfgs_solve": (C.c_int, [_vp, C.POINTER(SlbfgsParams), _vp, _vp, _vp, C.c_longlong, C.POINTER(Record),
+                                   C.POINTER(SolveInfo)]),
+    "lbf_slbfgs_begin": (C.c_int, [_vp, C.POINTER(SlbfgsParams), _vp, _vp, _vp, C.c_longlong, C.POINTER(_vp)]),
+    "lbf_slbfgs_iterate": (C.c_int, [_vp, C.c_int, C.POINTER(Record), C.POINTER(SolveInfo)]),
+    "lbf_slbfgs_end": (C.c_int, [_vp]),
+    "lbf_slbfgs_pair0": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "lbf_slbfgs_pair_io": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "lbf_prof_enable": (C.c_int, [_vp, C.c_int]),
+    "lbf_prof_select": (C.c_int, [_vp, C.c_int]),
+    "lbf_prof_sample": (C.c_int, [_vp, C.c_int]),
+    "lbf_prof_read": (C.c_int, [_vp, C.c_int, _ip, _dp, C.POINTER(C.c_longlong), _ip]),
+    "lbf_prof_read_work": (C.c_int, [_vp, C.c_int, _ip, _dp, _ip]),
+    "lbf_synth_mnist": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_uint, _vp, _vp]),
+    "lbf_sample_indices": (C.c_int, [C.c_longlong, C.c_int, C.c_uint, C.c_int, _vp]),
+    "lbf_idx_read_images": (C.c_int, [C.c_char_p, C.c_longlong, _vp, C.POINTER(C.c_longlong), _ip, _ip]),
+    "lbf_idx_read_labels": (C.c_int, [C.c_char_p, C.c_longlong, C.c_int, _vp, C.POINTER(C.c_longlong)]),
+    "lbf_mlp_hvp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_double, _vp]),
+    "lbf_mlp_gnvp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_double, _vp]),
+    "lbf_mlp_loss": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, _dp]),
+    "lbf_mlp_fd_hvp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_double,
+                                 C.c_double, _vp]),
+    "lbf_gd_default_params": (None, [C.POINTER(GdParams)]),
+    "lbf_sgd_default_params": (None, [C.POINTER(SgdParams)]),
+    "lbf_gd_solve": (C.c_int, [_vp, C.POINTER(GdParams), _vp, _vp, _vp, C.c_longlong, C.c_longlong,
+                               C.POINTER(Record), C.POINTER(SolveInfo)]),
+    "lbf_sgd_solve": (C.c_int, [_vp, C.POINTER(SgdParams), _vp, _vp, _vp, C.c_longlong, C.POINTER(Record),
+                                C.POINTER(SolveInfo)]),
+    "lbf_synth_regression": (C.c_int, [_vp, C.c_longlong, C.c_longlong, C.c_int, C.c_uint, C.c_uint, _vp, _vp]),
+    "lbf_mlp_set_loss": (C.c_int, [_vp, C.c_int]),
+    "lbf_mlp_get_loss": (C.c_int, [_vp, _ip]),
+    "lbf_mlp_set_l2": (C.c_int, [_vp, C.c_double]),
+    "lbf_mlp_get_l2": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "lbf_cg_default_params": (None, [C.POINTER(CgParams)]),
+    "lbf_mlp_gn_cg": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.POINTER(CgParams), _vp,
+                                C.POINTER(CgInfo)]),
+    "lbf_mlp_gn_cg_residual": (C.c_int, [_vp, _vp]),
+    "lbf_hf_default_params": (None, [C.POINTER(HfParams)]),
+    "lbf_hf_solve": (C.c_int, [_vp, C.POINTER(HfParams), _vp, _vp, _vp, C.c_longlong, C.c_longlong,
+                               C.POINTER(Record), C.POINTER(SolveInfo)]),
+    "lbf_mlp_grad_sq": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, _vp]),
+    "lbf_mlp_gn_pcg": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.POINTER(CgParams),
+                                 _vp, C.POINTER(CgInfo)]),
+    "lbf_hf_precond_default": (None, [C.POINTER(HfPrecond)]),
+    "lbf_hf_solve_pc": (C.c_int, [_vp, C.POINTER(HfParams), C.POINTER(HfPrecond), _vp, _vp, _vp, C.c_longlong,
+                                  C.c_longlong, C.POINTER(Record), C.POINTER(SolveInfo)]),
+    "lbf_owlqn_default_params": (None, [C.POINTER(OwlqnParams)]),
+    "lbf_owlqn_solve": (C.c_int, [_vp, C.POINTER(OwlqnParams), _vp, _vp, _vp, C.c_longlong, C.c_longlong,
+                                  C.POINTER(Record), C.POINTER(SolveInfo), C.POINTER(OwlqnStats)]),
+    "lbf_mlp_l1_pseudo_grad": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_int, _vp, C.POINTER(OwlqnStats)]),
+    "lbf_mlp_l1_trial": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_int, C.c_float, _vp, _dp, _dp, _dp,
+                                   C.POINTER(C.c_longlong)]),
+    "lbf_adam_default_params": (None, [C.POINTER(AdamParams)]),
+    "lbf_adam_coefs": (C.c_int, [C.POINTER(AdamParams), C.c_double, C.c_longlong, C.POINTER(AdamCoef)]),
+    "lbf_adam_epoch_orders": (C.c_int, [C.c_longlong, C.c_uint, C.c_int, _vp]),
+    "lbf_adam_step": (C.c_int, [_vp, C.c_longlong, C.POINTER(AdamCoef), _vp, _vp, _vp, _vp, _vp]),
+    "lbf_adam_solve": (C.c_int, [_vp, C.POINTER(AdamParams), _vp, _vp, _vp, C.c_longlong, C.POINTER(Record),
+                                 C.POINTER(SolveInfo)]),
+    "lbf_adam_begin": (C.c_int, [_vp, C.POINTER(AdamParams), _vp, _vp, _vp, C.c_longlong, C.POINTER(_vp)]),
+    "lbf_adam_iterate": (C.c_int, [_vp, C.c_int, C.POINTER(Record), C.POINTER(SolveInfo), _ip]),
+    "lbf_adam_end": (C.c_int, [_vp]),
+    "lbf_mlp_evaluate": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_int, C.c_longlong,
+                                   C.POINTER(EvalResultC), _vp, _vp, _vp]),
+}
+EXPORTS = tuple(_SIG)
+
 
 def lib():
     """Load the HIP library (raises LbfError if it is missing: there is no fallback)."""
@@ -124,110 +230,7 @@ def lib():
         raise LbfError(f"{os.path.basename(LIB_PATH)} not built ({LIB_PATH}); run `make -C lbfgs-ffnn_amd` or "
                        "__graft_entry__.build()")
     L = C.CDLL(LIB_PATH)
-    sig = {
-        "lbf_last_error": (C.c_char_p, []),
-        "lbf_version": (C.c_char_p, []),
-        "lbf_abi_version": (C.c_int, []),
-        "lbf_ctx_create": (C.c_int, [C.c_int, _vp, C.POINTER(_vp)]),
-        "lbf_ctx_destroy": (C.c_int, [_vp]),
-        "lbf_ctx_sync": (C.c_int, [_vp]),
-        "lbf_ctx_stream": (_vp, [_vp]),
-        "lbf_comm_unique_id": (C.c_int, [C.c_char_p]),
-        "lbf_comm_init": (C.c_int, [_vp, C.c_int, C.c_int, C.c_char_p]),
-        "lbf_comm_init_local": (C.c_int, [C.POINTER(_vp), C.c_int]),
-        "lbf_comm_rank": (C.c_int, [_vp, _ip, _ip]),
-        "lbf_allreduce_sum": (C.c_int, [_vp, _vp, C.c_size_t]),
-        "lbf_mlp_create": (C.c_int, [_vp, C.c_int, _ip, _ip, C.POINTER(_vp)]),
-        "lbf_mlp_destroy": (C.c_int, [_vp]),
-        "lbf_mlp_param_count": (C.c_longlong, [_vp]),
-        "lbf_mlp_init_params": (C.c_int, [_vp, C.c_uint, C.c_int, _vp]),
-        "lbf_init_params_host": (C.c_int, [C.c_int, _ip, _ip, C.c_uint, C.c_int, _vp]),
-        "lbf_mlp_forward": (C.c_int, [_vp, _vp, _vp, C.c_longlong, _vp]),
-        "lbf_mlp_loss_grad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_double, _dp]),
-        "lbf_mlp_batch_grads": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_longlong, C.c_double, C.c_double, _vp,
-                                          C.c_longlong]),
-        "lbf_two_loop": (C.c_int, [_vp, C.c_longlong, C.c_int, _vp, _vp, _dp, _vp, _vp, C.c_int]),
-        "lbf_dot": (C.c_int, [_vp, C.c_longlong, _vp, _vp, _dp]),
-        "lbf_nrm2": (C.c_int, [_vp, C.c_longlong, _vp, _dp]),
-        "lbf_axpy": (C.c_int, [_vp, C.c_longlong, C.c_float, _vp, _vp]),
-        "lbf_scal": (C.c_int, [_vp, C.c_longlong, C.c_float, _vp]),
-        "lbf_lbfgs_default_params": (None, [C.POINTER(LbfgsParams), C.c_int]),
-        "lbf_slbfgs_default_params": (None, [C.POINTER(SlbfgsParams)]),
-        "lbf_lbfgs_solve": (C.c_int, [_vp, C.POINTER(LbfgsParams), _vp, _vp, _vp, C.c_longlong, C.c_longlong,
-                                      C.POINTER(Record), C.POINTER(SolveInfo)]),
-        "lbf_lbfgs_begin": (C.c_int, [_vp, C.POINTER(LbfgsParams), _vp, _vp, _vp, C.c_longlong, C.c_longlong,
-                                      C.POINTER(_vp)]),
-        "lbf_lbfgs_iterate": (C.c_int, [_vp, C.c_int, C.POINTER(Record), C.POINTER(SolveInfo)]),
-        "lbf_lbfgs_end": (C.c_int, [_vp]),
-        "lbf_lbfgs_solve_fn": (C.c_int, [_vp, C.POINTER(LbfgsParams), C.c_longlong, _vp, _vp, _vp,
-                                         C.POINTER(Record), C.POINTER(SolveInfo)]),
-        "lbf_device_alloc": (C.c_int, [_vp, C.c_size_t, C.POINTER(_vp)]),
-        "lbf_device_free": (C.c_int, [_vp, _vp]),
-        "lbf_memcpy": (C.c_int, [_vp, _vp, _vp, C.c_size_t, C.c_int]),
-        "lbf_slbfgs_solve": (C.c_int, [_vp, C.POINTER(SlbfgsParams), _vp, _vp, _vp, C.c_longlong, C.POINTER(Record),
-                                       C.POINTER(SolveInfo)]),
-        "lbf_slbfgs_begin": (C.c_int, [_vp, C.POINTER(SlbfgsParams), _vp, _vp, _vp, C.c_longlong, C.POINTER(_vp)]),
-        "lbf_slbfgs_iterate": (C.c_int, [_vp, C.c_int, C.POINTER(Record), C.POINTER(SolveInfo)]),
-        "lbf_slbfgs_end": (C.c_int, [_vp]),
-        "lbf_slbfgs_pair0": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
-        "lbf_slbfgs_pair_io": (C.c_int, [_vp, C.c_int, _vp, _vp]),
-        "lbf_prof_enable": (C.c_int, [_vp, C.c_int]),
-        "lbf_prof_select": (C.c_int, [_vp, C.c_int]),
-        "lbf_prof_sample": (C.c_int, [_vp, C.c_int]),
-        "lbf_prof_read": (C.c_int, [_vp, C.c_int, _ip, _dp, C.POINTER(C.c_longlong), _ip]),
-        "lbf_prof_read_work": (C.c_int, [_vp, C.c_int, _ip, _dp, _ip]),
-        "lbf_synth_mnist": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_uint, _vp, _vp]),
-        "lbf_sample_indices": (C.c_int, [C.c_longlong, C.c_int, C.c_uint, C.c_int, _vp]),
-        "lbf_idx_read_images": (C.c_int, [C.c_char_p, C.c_longlong, _vp, C.POINTER(C.c_longlong), _ip, _ip]),
-        "lbf_idx_read_labels": (C.c_int, [C.c_char_p, C.c_longlong, C.c_int, _vp, C.POINTER(C.c_longlong)]),
-        "lbf_mlp_hvp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_double, _vp]),
-        "lbf_mlp_gnvp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_double, _vp]),
-        "lbf_mlp_loss": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, _dp]),
-        "lbf_mlp_fd_hvp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_double,
-                                     C.c_double, _vp]),
-        "lbf_gd_default_params": (None, [C.POINTER(GdParams)]),
-        "lbf_sgd_default_params": (None, [C.POINTER(SgdParams)]),
-        "lbf_gd_solve": (C.c_int, [_vp, C.POINTER(GdParams), _vp, _vp, _vp, C.c_longlong, C.c_longlong,
-                                   C.POINTER(Record), C.POINTER(SolveInfo)]),
-        "lbf_sgd_solve": (C.c_int, [_vp, C.POINTER(SgdParams), _vp, _vp, _vp, C.c_longlong, C.POINTER(Record),
-                                    C.POINTER(SolveInfo)]),
-        "lbf_synth_regression": (C.c_int, [_vp, C.c_longlong, C.c_longlong, C.c_int, C.c_uint, C.c_uint, _vp, _vp]),
-        "lbf_mlp_set_loss": (C.c_int, [_vp, C.c_int]),
-        "lbf_mlp_get_loss": (C.c_int, [_vp, _ip]),
-        "lbf_mlp_set_l2": (C.c_int, [_vp, C.c_double]),
-        "lbf_mlp_get_l2": (C.c_int, [_vp, C.POINTER(C.c_double)]),
-        "lbf_cg_default_params": (None, [C.POINTER(CgParams)]),
-        "lbf_mlp_gn_cg": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.POINTER(CgParams), _vp,
-                                    C.POINTER(CgInfo)]),
-        "lbf_mlp_gn_cg_residual": (C.c_int, [_vp, _vp]),
-        "lbf_hf_default_params": (None, [C.POINTER(HfParams)]),
-        "lbf_hf_solve": (C.c_int, [_vp, C.POINTER(HfParams), _vp, _vp, _vp, C.c_longlong, C.c_longlong,
-                                   C.POINTER(Record), C.POINTER(SolveInfo)]),
-        "lbf_mlp_grad_sq": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, _vp]),
-        "lbf_mlp_gn_pcg": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.POINTER(CgParams),
-                                     _vp, C.POINTER(CgInfo)]),
-        "lbf_hf_precond_default": (None, [C.POINTER(HfPrecond)]),
-        "lbf_hf_solve_pc": (C.c_int, [_vp, C.POINTER(HfParams), C.POINTER(HfPrecond), _vp, _vp, _vp, C.c_longlong,
-                                      C.c_longlong, C.POINTER(Record), C.POINTER(SolveInfo)]),
-        "lbf_owlqn_default_params": (None, [C.POINTER(OwlqnParams)]),
-        "lbf_owlqn_solve": (C.c_int, [_vp, C.POINTER(OwlqnParams), _vp, _vp, _vp, C.c_longlong, C.c_longlong,
-                                      C.POINTER(Record), C.POINTER(SolveInfo), C.POINTER(OwlqnStats)]),
-        "lbf_mlp_l1_pseudo_grad": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_int, _vp, C.POINTER(OwlqnStats)]),
-        "lbf_mlp_l1_trial": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_int, C.c_float, _vp, _dp, _dp, _dp,
-                                       C.POINTER(C.c_longlong)]),
-        "lbf_adam_default_params": (None, [C.POINTER(AdamParams)]),
-        "lbf_adam_coefs": (C.c_int, [C.POINTER(AdamParams), C.c_double, C.c_longlong, C.POINTER(AdamCoef)]),
-        "lbf_adam_epoch_orders": (C.c_int, [C.c_longlong, C.c_uint, C.c_int, _vp]),
-        "lbf_adam_step": (C.c_int, [_vp, C.c_longlong, C.POINTER(AdamCoef), _vp, _vp, _vp, _vp, _vp]),
-        "lbf_adam_solve": (C.c_int, [_vp, C.POINTER(AdamParams), _vp, _vp, _vp, C.c_longlong, C.POINTER(Record),
-                                     C.POINTER(SolveInfo)]),
-        "lbf_adam_begin": (C.c_int, [_vp, C.POINTER(AdamParams), _vp, _vp, _vp, C.c_longlong, C.POINTER(_vp)]),
-        "lbf_adam_iterate": (C.c_int, [_vp, C.c_int, C.POINTER(Record), C.POINTER(SolveInfo), _ip]),
-        "lbf_adam_end": (C.c_int, [_vp]),
-        "lbf_mlp_evaluate": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_int, C.c_longlong,
-                                       C.POINTER(EvalResultC), _vp, _vp, _vp]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in _SIG.items():
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args
@@ -235,21 +238,6 @@ def lib():
         raise LbfError(f"{LIB_PATH} implements ABI {L.lbf_abi_version()}, this binding needs {ABI_VERSION}: rebuild it")
     _lib = L
     return L
-
-
-EXPORTS = ("lbf_last_error lbf_version lbf_abi_version lbf_ctx_create lbf_ctx_destroy lbf_ctx_sync lbf_ctx_stream "
-           "lbf_comm_unique_id lbf_comm_init lbf_comm_init_local lbf_comm_rank lbf_allreduce_sum lbf_mlp_create lbf_mlp_destroy "
-           "lbf_mlp_param_count lbf_mlp_init_params lbf_init_params_host lbf_mlp_forward lbf_mlp_loss_grad lbf_mlp_batch_grads lbf_two_loop lbf_dot "
-           "lbf_nrm2 lbf_axpy lbf_scal lbf_lbfgs_default_params lbf_slbfgs_default_params lbf_lbfgs_solve "
-           "lbf_lbfgs_begin lbf_lbfgs_iterate lbf_lbfgs_end lbf_lbfgs_solve_fn lbf_device_alloc lbf_device_free lbf_memcpy lbf_slbfgs_solve lbf_slbfgs_begin lbf_slbfgs_iterate lbf_slbfgs_end lbf_slbfgs_pair0 lbf_slbfgs_pair_io lbf_prof_enable lbf_prof_select lbf_prof_sample lbf_prof_read lbf_prof_read_work lbf_synth_mnist "
-           "lbf_sample_indices lbf_synth_regression lbf_gd_default_params lbf_sgd_default_params lbf_gd_solve "
-           "lbf_sgd_solve lbf_idx_read_images lbf_idx_read_labels lbf_mlp_hvp lbf_mlp_fd_hvp lbf_mlp_loss "
-           "lbf_mlp_set_loss lbf_mlp_get_loss lbf_mlp_set_l2 lbf_mlp_get_l2 lbf_mlp_evaluate lbf_mlp_gnvp "
-           "lbf_cg_default_params lbf_mlp_gn_cg lbf_mlp_gn_cg_residual lbf_hf_default_params lbf_hf_solve "
-           "lbf_owlqn_default_params lbf_owlqn_solve lbf_mlp_l1_pseudo_grad lbf_mlp_l1_trial "
-           "lbf_mlp_grad_sq lbf_mlp_gn_pcg lbf_hf_precond_default lbf_hf_solve_pc "
-           "lbf_adam_default_params lbf_adam_coefs lbf_adam_epoch_orders lbf_adam_step lbf_adam_solve lbf_adam_begin "
-           "lbf_adam_iterate lbf_adam_end").split()
 
 
 def check_precond(name) -> int:

@@ -50,6 +50,36 @@ template <class F> int guard(F &&f) {
 void check_comm(ncclResult_t r, const char *what) {
   if (r != ncclSuccess) throw Error(LBF_ERR_COMM, std::string(what) + ": " + ncclGetErrorString(r));
 }
+
+void check_memory(const lbf_lbfgs_params &prm) { LBF_REQUIRE(prm.m >= 0 && prm.m <= 128, "m in [0, 128]"); }
+
+// lbf_mlp_gn_cg (d_minv null) and lbf_mlp_gn_pcg
+void gn_cg(lbf_mlp *net, const float *d_params, const float *d_b, const float *d_minv, const float *d_X,
+           const float *d_Y, const int *d_idx, long long batch, double inv_scale, const lbf_cg_params *prm, float *d_x,
+           lbf_cg_info *info) {
+  net->ctx->c.set_device();
+  Mlp::CgInfo ci;
+  net->net->gn_cg(d_params, d_b, 1.0f, d_X, d_Y, d_idx, batch, inv_scale, prm->damping, prm->max_iters, prm->rtol,
+                  prm->check, d_x, &ci, d_minv);
+  if (info) *info = lbf_cg_info{ci.iterations, ci.status, ci.rr0, ci.rr, ci.xb, ci.xr, ci.xx};
+}
+
+// lbf_prof_read (values: total ms, counts) and lbf_prof_read_work (values: work units, no counts): the sections
+// that were timed, the first `cap` of them written, all of them counted
+void prof_read(lbf_ctx *ctx, const std::vector<double> &src, int cap, int *ids, double *values, long long *counts,
+               int *n_out) {
+  int k = 0;
+  for (size_t i = 0; i < ctx->c.prof.cnt.size(); ++i) {
+    if (ctx->c.prof.cnt[i] == 0) continue;
+    if (k < cap) {
+      if (ids) ids[k] = int(i);
+      if (values) values[k] = i < src.size() ? src[i] : 0.0;
+      if (counts) counts[k] = ctx->c.prof.cnt[i];
+    }
+    ++k;
+  }
+  *n_out = k;
+}
 } // namespace
 
 extern "C" {
@@ -61,32 +91,27 @@ int lbf_abi_version(void) { return LBF_ABI_VERSION; }
 int lbf_ctx_create(int device, void *stream, lbf_ctx **out) {
   return guard([&] {
     LBF_REQUIRE(out, "out");
-    auto *c = new lbf_ctx();
+    auto c = std::make_unique<lbf_ctx>();
     c->c.device = device;
-    try {
-      c->c.set_device();
-      int cus = 0;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
-        c->c.cus = cus;
-      if (stream) {
-        c->c.stream = static_cast<hipStream_t>(stream);
-      } else {
-        // blocking: ordered with the legacy stream torch uses; the highest priority, so that a solver's
-        // critical chain is dispatched ahead of its own off-path work (the S-LBFGS twin, lowest priority)
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest < least)
-          LBF_HIP(hipStreamCreateWithPriority(&c->c.stream, hipStreamDefault, greatest));
-        else
-          LBF_HIP(hipStreamCreateWithFlags(&c->c.stream, hipStreamDefault));
-        c->c.own_stream = true;
-      }
-      c->scal.resize(SC_N);
-      LBF_HIP(hipMemset(c->scal.get(), 0, SC_N * sizeof(double)));
-    } catch (...) {
-      delete c;
-      throw;
+    c->c.set_device();
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
+      c->c.cus = cus;
+    if (stream) {
+      c->c.stream = static_cast<hipStream_t>(stream);
+    } else {
+      // blocking: ordered with the legacy stream torch uses; the highest priority, so that a solver's
+      // critical chain is dispatched ahead of its own off-path work (the S-LBFGS twin, lowest priority)
+      int least = 0, greatest = 0;
+      if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest < least)
+        LBF_HIP(hipStreamCreateWithPriority(&c->c.stream, hipStreamDefault, greatest));
+      else
+        LBF_HIP(hipStreamCreateWithFlags(&c->c.stream, hipStreamDefault));
+      c->c.own_stream = true;
     }
-    *out = c;
+    c->scal.resize(SC_N);
+    LBF_HIP(hipMemset(c->scal.get(), 0, SC_N * sizeof(double)));
+    *out = c.release();
   });
 }
 
@@ -164,15 +189,10 @@ int lbf_mlp_create(lbf_ctx *ctx, int nlayers, const int *dims, const int *acts, 
   return guard([&] {
     LBF_REQUIRE(ctx && dims && acts && out, "null argument");
     ctx->c.set_device();
-    auto *m = new lbf_mlp();
+    auto m = std::make_unique<lbf_mlp>();
     m->ctx = ctx;
-    try {
-      m->net.reset(new Mlp(&ctx->c, nlayers, dims, acts, read_switches()));
-    } catch (...) {
-      delete m;
-      throw;
-    }
-    *out = m;
+    m->net.reset(new Mlp(&ctx->c, nlayers, dims, acts, read_switches()));
+    *out = m.release();
   });
 }
 
@@ -527,19 +547,7 @@ int lbf_mlp_gn_cg(lbf_mlp *net, const float *d_params, const float *d_b, const f
                   lbf_cg_info *info) {
   return guard([&] {
     LBF_REQUIRE(net && prm && d_params && d_b && d_x && batch >= 0 && (batch == 0 || (d_X && d_Y)), "bad argument");
-    net->ctx->c.set_device();
-    Mlp::CgInfo ci;
-    net->net->gn_cg(d_params, d_b, 1.0f, d_X, d_Y, d_idx, batch, inv_scale, prm->damping, prm->max_iters, prm->rtol,
-                    prm->check, d_x, &ci);
-    if (info) {
-      info->iterations = ci.iterations;
-      info->status = ci.status;
-      info->rr0 = ci.rr0;
-      info->rr = ci.rr;
-      info->xb = ci.xb;
-      info->xr = ci.xr;
-      info->xx = ci.xx;
-    }
+    gn_cg(net, d_params, d_b, nullptr, d_X, d_Y, d_idx, batch, inv_scale, prm, d_x, info);
   });
 }
 
@@ -549,19 +557,7 @@ int lbf_mlp_gn_pcg(lbf_mlp *net, const float *d_params, const float *d_b, const 
   return guard([&] {
     LBF_REQUIRE(net && prm && d_params && d_b && d_minv && d_x && batch >= 0 && (batch == 0 || (d_X && d_Y)),
                 "bad argument");
-    net->ctx->c.set_device();
-    Mlp::CgInfo ci;
-    net->net->gn_cg(d_params, d_b, 1.0f, d_X, d_Y, d_idx, batch, inv_scale, prm->damping, prm->max_iters, prm->rtol,
-                    prm->check, d_x, &ci, d_minv);
-    if (info) {
-      info->iterations = ci.iterations;
-      info->status = ci.status;
-      info->rr0 = ci.rr0;
-      info->rr = ci.rr;
-      info->xb = ci.xb;
-      info->xr = ci.xr;
-      info->xx = ci.xx;
-    }
+    gn_cg(net, d_params, d_b, d_minv, d_X, d_Y, d_idx, batch, inv_scale, prm, d_x, info);
   });
 }
 
@@ -778,14 +774,9 @@ int lbf_adam_begin(lbf_mlp *net, const lbf_adam_params *prm, float *d_params, co
     LBF_REQUIRE(N >= 1 && N < (1LL << 31), "N must lie in [1, 2^31)");
     LBF_REQUIRE(net && d_params && d_X && d_Y, "null argument");
     net->ctx->c.set_device();
-    auto *h = new lbf_adam();
-    try {
-      h->s.reset(new AdamSolver(net->net.get(), *prm, d_params, d_X, d_Y, N));
-    } catch (...) {
-      delete h;
-      throw;
-    }
-    *out = h;
+    auto h = std::make_unique<lbf_adam>();
+    h->s.reset(new AdamSolver(net->net.get(), *prm, d_params, d_X, d_Y, N));
+    *out = h.release();
   });
 }
 
@@ -834,20 +825,15 @@ int lbf_lbfgs_begin(lbf_mlp *net, const lbf_lbfgs_params *prm, float *d_params, 
                     const float *d_Y, long long n_local, long long n_global, lbf_lbfgs **out) {
   return guard([&] {
     LBF_REQUIRE(net && prm && out, "null argument");
-    LBF_REQUIRE(prm->m >= 0 && prm->m <= 128, "m in [0, 128]");
+    check_memory(*prm);
     net->ctx->c.set_device();
     // a data-parallel rank with an empty shard (n_local == 0) has no data pointers
     LBF_REQUIRE(d_params && (n_local == 0 || (d_X && d_Y)), "null pointer");
     LBF_REQUIRE(n_local >= 0 && n_global > 0, "batch sizes");
-    auto *s = new lbf_lbfgs();
-    try {
-      s->obj.reset(new MlpObjective(net->net.get(), d_X, d_Y, n_local, n_global));
-      s->s.reset(new LbfgsSolver(s->obj.get(), *prm, d_params, read_switches()));
-    } catch (...) {
-      delete s;
-      throw;
-    }
-    *out = s;
+    auto s = std::make_unique<lbf_lbfgs>();
+    s->obj.reset(new MlpObjective(net->net.get(), d_X, d_Y, n_local, n_global));
+    s->s.reset(new LbfgsSolver(s->obj.get(), *prm, d_params, read_switches()));
+    *out = s.release();
   });
 }
 
@@ -888,7 +874,7 @@ int lbf_lbfgs_solve_fn(lbf_ctx *ctx, const lbf_lbfgs_params *prm, long long n, f
   }
   return guard([&] {
     LBF_REQUIRE(ctx && prm && fn, "null argument");
-    LBF_REQUIRE(prm->m >= 0 && prm->m <= 128, "m in [0, 128]");
+    check_memory(*prm);
     ctx->c.set_device();
     CallbackObjective obj(&ctx->c, n, fn, user);
     LbfgsSolver s(&obj, *prm, d_params, read_switches());
@@ -944,14 +930,9 @@ int lbf_slbfgs_begin(lbf_mlp *net, const lbf_slbfgs_params *prm, float *d_params
   return guard([&] {
     LBF_REQUIRE(net && prm && out, "null argument");
     net->ctx->c.set_device();
-    auto *h = new lbf_slbfgs();
-    try {
-      h->s.reset(new SlbfgsSolver(net->net.get(), *prm, d_params, d_X, d_Y, N, read_switches()));
-    } catch (...) {
-      delete h;
-      throw;
-    }
-    *out = h;
+    auto h = std::make_unique<lbf_slbfgs>();
+    h->s.reset(new SlbfgsSolver(net->net.get(), *prm, d_params, d_X, d_Y, N, read_switches()));
+    *out = h.release();
   });
 }
 
@@ -1014,17 +995,7 @@ int lbf_prof_read(lbf_ctx *ctx, int cap, int *ids, double *ms, long long *counts
     LBF_REQUIRE(ctx && n_out, "null argument");
     ctx->c.set_device();
     ctx->c.prof.resolve();
-    int k = 0;
-    for (size_t i = 0; i < ctx->c.prof.cnt.size(); ++i) {
-      if (ctx->c.prof.cnt[i] == 0) continue;
-      if (k < cap) {
-        if (ids) ids[k] = int(i);
-        if (ms) ms[k] = ctx->c.prof.ms[i];
-        if (counts) counts[k] = ctx->c.prof.cnt[i];
-      }
-      ++k;
-    }
-    *n_out = k;
+    prof_read(ctx, ctx->c.prof.ms, cap, ids, ms, counts, n_out);
   });
 }
 
@@ -1033,16 +1004,7 @@ int lbf_prof_read_work(lbf_ctx *ctx, int cap, int *ids, double *work, int *n_out
     LBF_REQUIRE(ctx && n_out, "null argument");
     ctx->c.set_device();
     ctx->c.prof.resolve();
-    int k = 0;
-    for (size_t i = 0; i < ctx->c.prof.cnt.size(); ++i) {
-      if (ctx->c.prof.cnt[i] == 0) continue;
-      if (k < cap) {
-        if (ids) ids[k] = int(i);
-        if (work) work[k] = i < ctx->c.prof.work.size() ? ctx->c.prof.work[i] : 0.0;
-      }
-      ++k;
-    }
-    *n_out = k;
+    prof_read(ctx, ctx->c.prof.work, cap, ids, work, nullptr, n_out);
   });
 }
 

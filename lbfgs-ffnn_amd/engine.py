@@ -14,11 +14,10 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import (ACTS, HVP_MODES, INIT_CPU, INIT_CUDA, LOSSES, PRECONDS, HfPrecond, check_l2, check_precond, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED, SLBFGS_DP_SLICED,
-                   AdamCoef, AdamParams, CgInfo, CgParams, EvalResultC, GdParams, HfParams, LbfError, LbfgsParams, OwlqnParams, OwlqnStats, Record, SgdParams, SlbfgsParams, SolveInfo, check, lib,
-                   ptr)
-
-_check_rc = check  # for Mlp.gn_cg, whose `check` argument is the CG status-read interval
+from ._lib import (ACTS, HVP_MODES, INIT_CPU, INIT_CUDA, LOSSES, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED,
+                   SLBFGS_DP_SLICED, AdamCoef, AdamParams, CgInfo, CgParams, EvalResultC, GdParams, HfParams,
+                   HfPrecond, LbfError, LbfgsParams, OwlqnParams, OwlqnStats, Record, SgdParams, SlbfgsParams,
+                   SolveInfo, check, check_l2, check_precond, lib, ptr)
 
 
 class Context:
@@ -116,36 +115,28 @@ class Context:
         """Time only every `every`-th launch of the selected sections."""
         check(lib().lbf_prof_sample(self.h, int(every)), "lbf_prof_sample")
 
-    def prof_read_work(self):
-        """{section name: work units of the timed launches} (GEMM sections: batch rows)."""
-        n = C.c_int(0)
-        check(lib().lbf_prof_read_work(self.h, 0, None, None, C.byref(n)), "lbf_prof_read_work")
+    def _prof_read(self, name, *ctypes):
+        """[(section name, values...)] of lbf_prof_read / lbf_prof_read_work: one output array per ctype."""
+        fn, n = getattr(lib(), name), C.c_int(0)
+        check(fn(self.h, 0, None, *[None] * len(ctypes), C.byref(n)), name)
         cap = n.value
         ids = (C.c_int * max(cap, 1))()
-        work = (C.c_double * max(cap, 1))()
-        check(lib().lbf_prof_read_work(self.h, cap, ids, work, C.byref(n)), "lbf_prof_read_work")
-        out = {}
+        cols = [(t * max(cap, 1))() for t in ctypes]
+        check(fn(self.h, cap, ids, *cols, C.byref(n)), name)
+        out = []
         for i in range(min(cap, n.value)):
             kind, layer = divmod(ids[i], 16)
-            name = self.PROF_KINDS[kind] if kind < len(self.PROF_KINDS) else f"k{kind}"
-            out[f"{name}[{layer}]"] = work[i]
+            kname = self.PROF_KINDS[kind] if kind < len(self.PROF_KINDS) else f"k{kind}"
+            out.append((f"{kname}[{layer}]", *[c[i] for c in cols]))
         return out
+
+    def prof_read_work(self):
+        """{section name: work units of the timed launches} (GEMM sections: batch rows)."""
+        return dict(self._prof_read("lbf_prof_read_work", C.c_double))
 
     def prof_read(self):
         """{section name: (total ms, launches)}; section = kind[layer]."""
-        n = C.c_int(0)
-        check(lib().lbf_prof_read(self.h, 0, None, None, None, C.byref(n)), "lbf_prof_read")
-        cap = n.value
-        ids = (C.c_int * max(cap, 1))()
-        ms = (C.c_double * max(cap, 1))()
-        cnt = (C.c_longlong * max(cap, 1))()
-        check(lib().lbf_prof_read(self.h, cap, ids, ms, cnt, C.byref(n)), "lbf_prof_read")
-        out = {}
-        for i in range(min(cap, n.value)):
-            kind, layer = divmod(ids[i], 16)
-            name = self.PROF_KINDS[kind] if kind < len(self.PROF_KINDS) else f"k{kind}"
-            out[f"{name}[{layer}]"] = (ms[i], int(cnt[i]))
-        return out
+        return {k: (ms, int(cnt)) for k, ms, cnt in self._prof_read("lbf_prof_read", C.c_double, C.c_longlong)}
 
     def __del__(self):
         try:
@@ -228,6 +219,17 @@ class Mlp:
         if Y is not None and (Y.dim() != 2 or Y.shape[1] != self.dims[-1] or Y.shape[0] != X.shape[0]):
             raise LbfError(f"Y must be [{X.shape[0]}][{self.dims[-1]}], got {tuple(Y.shape)}")
 
+    def _batch(self, X, Y, idx, scale, out=False):
+        """The prologue of a batch evaluation: (rows, `scale` or 1 / rows, `out` or, for None, a new parameter-sized
+        tensor), after the shape check of X / Y."""
+        B = int(idx.numel()) if idx is not None else int(X.shape[0])
+        if scale is None:
+            scale = 1.0 / max(B, 1)
+        if out is None:
+            out = self.new_params()
+        self._check_data(X, Y)
+        return B, scale, out
+
     def new_params(self) -> torch.Tensor:
         return torch.empty(self.nparams, dtype=torch.float32, device=f"cuda:{self.ctx.device}")
 
@@ -247,11 +249,7 @@ class Mlp:
     def loss_grad(self, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, idx: Optional[torch.Tensor] = None,
                   inv_scale: Optional[float] = None, l2: float = 0.0, grad: Optional[torch.Tensor] = None):
         """LossGradFun (src/cuda/minimizer_base.cuh:15-16): returns (loss, grad)."""
-        B = int(idx.numel()) if idx is not None else int(X.shape[0])
-        if inv_scale is None:
-            inv_scale = 1.0 / max(B, 1)
-        grad = self.new_params() if grad is None else grad
-        self._check_data(X, Y)
+        B, inv_scale, grad = self._batch(X, Y, idx, inv_scale, grad)
         loss = C.c_double()
         check(lib().lbf_mlp_loss_grad(self.h, ptr(params, numel=self.nparams), ptr(grad, numel=self.nparams), ptr(X),
                                       ptr(Y), ptr(idx, torch.int32), B, inv_scale, l2, C.byref(loss)),
@@ -279,10 +277,7 @@ class Mlp:
     def loss(self, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, idx: Optional[torch.Tensor] = None,
              inv_scale: Optional[float] = None) -> float:
         """Forward + MSE only (lbf_mlp_loss): the f of a line-search trial."""
-        B = int(idx.numel()) if idx is not None else int(X.shape[0])
-        if inv_scale is None:
-            inv_scale = 1.0 / max(B, 1)
-        self._check_data(X, Y)
+        B, inv_scale, _ = self._batch(X, Y, idx, inv_scale)
         out = C.c_double()
         check(lib().lbf_mlp_loss(self.h, ptr(params, numel=self.nparams), ptr(X), ptr(Y), ptr(idx, torch.int32), B,
                                  inv_scale, C.byref(out)), "lbf_mlp_loss")
@@ -329,14 +324,14 @@ class Mlp:
             idx: Optional[torch.Tensor] = None, inv_scale: Optional[float] = None, l2: float = 0.0,
             out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Exact H(params) v of the loss_grad batch loss (R-operator, lbf_mlp_hvp)."""
-        B = int(idx.numel()) if idx is not None else int(X.shape[0])
-        if inv_scale is None:
-            inv_scale = 1.0 / max(B, 1)
-        out = self.new_params() if out is None else out
-        self._check_data(X, Y)
+        return self._product("lbf_mlp_hvp", params, v, X, Y, idx, inv_scale, l2, out)
+
+    def _product(self, name, params, v, X, Y, idx, inv_scale, l2, out, *eps):
+        """hvp, gnvp and fd_hvp (whose eps follows l2): one call shape, `name` the entry point."""
+        B, inv_scale, out = self._batch(X, Y, idx, inv_scale, out)
         n = self.nparams
-        check(lib().lbf_mlp_hvp(self.h, ptr(params, numel=n), ptr(v, numel=n), ptr(X), ptr(Y), ptr(idx, torch.int32),
-                                B, inv_scale, l2, ptr(out, numel=n)), "lbf_mlp_hvp")
+        check(getattr(lib(), name)(self.h, ptr(params, numel=n), ptr(v, numel=n), ptr(X), ptr(Y),
+                                   ptr(idx, torch.int32), B, inv_scale, l2, *eps, ptr(out, numel=n)), name)
         return out
 
     def gnvp(self, params: torch.Tensor, v: torch.Tensor, X: torch.Tensor, Y: torch.Tensor,
@@ -344,15 +339,7 @@ class Mlp:
              out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Gauss-Newton product G(params) v + l2 v of the loss_grad batch loss (lbf_mlp_gnvp): G = J^T H_L J,
         positive semi-definite, split at the outputs for "mse" and at the logits for "softmax_xent"."""
-        B = int(idx.numel()) if idx is not None else int(X.shape[0])
-        if inv_scale is None:
-            inv_scale = 1.0 / max(B, 1)
-        out = self.new_params() if out is None else out
-        self._check_data(X, Y)
-        n = self.nparams
-        check(lib().lbf_mlp_gnvp(self.h, ptr(params, numel=n), ptr(v, numel=n), ptr(X), ptr(Y), ptr(idx, torch.int32),
-                                 B, inv_scale, l2, ptr(out, numel=n)), "lbf_mlp_gnvp")
-        return out
+        return self._product("lbf_mlp_gnvp", params, v, X, Y, idx, inv_scale, l2, out)
 
     def gn_cg(self, params: torch.Tensor, b: torch.Tensor, X: torch.Tensor, Y: torch.Tensor,
               idx: Optional[torch.Tensor] = None, inv_scale: Optional[float] = None, l2: float = 0.0,
@@ -363,26 +350,28 @@ class Mlp:
         scalar on the device; `check` iterations are enqueued between two status reads and the result does not
         depend on it. Returns (x, info): info has iterations, status (0 converged to rtol, 1 max_iters, 2 p.Ap <= 0),
         rr0, rr, xb, xr, xx and, with residual=True, "r": the recurrence residual as a tensor."""
-        B = int(idx.numel()) if idx is not None else int(X.shape[0])
-        if inv_scale is None:
-            inv_scale = 1.0 / max(B, 1)
-        out = self.new_params() if out is None else out
-        self._check_data(X, Y)
+        return self._gn_cg(params, b, None, X, Y, idx, inv_scale, l2, damping, max_iters, rtol, check, out, residual)
+
+    def _gn_cg(self, params, b, minv, X, Y, idx, inv_scale, l2, damping, max_iters, rtol, every, out, residual):
+        """gn_cg (minv None: lbf_mlp_gn_cg) and gn_pcg (lbf_mlp_gn_pcg); `every` is their `check`."""
+        B, inv_scale, out = self._batch(X, Y, idx, inv_scale, out)
         n = self.nparams
         p = CgParams()
         lib().lbf_cg_default_params(C.byref(p))
         p.damping = float(l2) + (0.0 if damping is None else float(damping))
-        for k, v in (("max_iters", max_iters), ("rtol", rtol), ("check", check)):
+        for k, v in (("max_iters", max_iters), ("rtol", rtol), ("check", every)):
             if v is not None:
                 setattr(p, k, v)
         ci = CgInfo()
-        _check_rc(lib().lbf_mlp_gn_cg(self.h, ptr(params, numel=n), ptr(b, numel=n), ptr(X), ptr(Y),
-                                      ptr(idx, torch.int32), B, inv_scale, C.byref(p), ptr(out, numel=n),
-                                      C.byref(ci)), "lbf_mlp_gn_cg")
+        name = "lbf_mlp_gn_cg" if minv is None else "lbf_mlp_gn_pcg"
+        mp = () if minv is None else (ptr(minv, numel=n),)
+        check(getattr(lib(), name)(self.h, ptr(params, numel=n), ptr(b, numel=n), *mp, ptr(X), ptr(Y),
+                                   ptr(idx, torch.int32), B, inv_scale, C.byref(p), ptr(out, numel=n), C.byref(ci)),
+              name)
         info = {k: getattr(ci, k) for k, _ in CgInfo._fields_}
         if residual:
             r = torch.empty(n, dtype=torch.float32, device=out.device)
-            _check_rc(lib().lbf_mlp_gn_cg_residual(self.h, ptr(r, numel=n)), "lbf_mlp_gn_cg_residual")
+            check(lib().lbf_mlp_gn_cg_residual(self.h, ptr(r, numel=n)), "lbf_mlp_gn_cg_residual")
             info["r"] = r
         return out, info
 
@@ -394,28 +383,7 @@ class Mlp:
         diagonal, one entry > 0 per parameter. z = minv * r is never stored; the stopping test stays on r.r; status 2
         also covers a non-positive r.z. With minv all ones the result is bitwise gn_cg's. Other arguments and the
         return value as gn_cg."""
-        B = int(idx.numel()) if idx is not None else int(X.shape[0])
-        if inv_scale is None:
-            inv_scale = 1.0 / max(B, 1)
-        out = self.new_params() if out is None else out
-        self._check_data(X, Y)
-        n = self.nparams
-        p = CgParams()
-        lib().lbf_cg_default_params(C.byref(p))
-        p.damping = float(l2) + (0.0 if damping is None else float(damping))
-        for k, v in (("max_iters", max_iters), ("rtol", rtol), ("check", check)):
-            if v is not None:
-                setattr(p, k, v)
-        ci = CgInfo()
-        _check_rc(lib().lbf_mlp_gn_pcg(self.h, ptr(params, numel=n), ptr(b, numel=n), ptr(minv, numel=n), ptr(X),
-                                       ptr(Y), ptr(idx, torch.int32), B, inv_scale, C.byref(p), ptr(out, numel=n),
-                                       C.byref(ci)), "lbf_mlp_gn_pcg")
-        info = {k: getattr(ci, k) for k, _ in CgInfo._fields_}
-        if residual:
-            r = torch.empty(n, dtype=torch.float32, device=out.device)
-            _check_rc(lib().lbf_mlp_gn_cg_residual(self.h, ptr(r, numel=n)), "lbf_mlp_gn_cg_residual")
-            info["r"] = r
-        return out, info
+        return self._gn_cg(params, b, minv, X, Y, idx, inv_scale, l2, damping, max_iters, rtol, check, out, residual)
 
     def grad_sq(self, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, idx: Optional[torch.Tensor] = None,
                 scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -423,13 +391,9 @@ class Mlp:
         gradients of the data loss (l_b at inv_scale = 1, no l2 term), i.e. the diagonal of the empirical Fisher
         matrix, formed on the device without materialising a per-example gradient. scale defaults to 1 / rows.
         Bitwise reproducible; with a communicator the ranks' scaled sums are all-reduced."""
-        B = int(idx.numel()) if idx is not None else int(X.shape[0])
-        if scale is None:
-            scale = 1.0 / max(B, 1)
-        out = self.new_params() if out is None else out
-        self._check_data(X, Y)
+        B, scale, out = self._batch(X, Y, idx, scale, out)
         n = self.nparams
-        _check_rc(lib().lbf_mlp_grad_sq(self.h, ptr(params, numel=n), ptr(X), ptr(Y), ptr(idx, torch.int32), B,
+        check(lib().lbf_mlp_grad_sq(self.h, ptr(params, numel=n), ptr(X), ptr(Y), ptr(idx, torch.int32), B,
                                         float(scale), ptr(out, numel=n)), "lbf_mlp_grad_sq")
         return out
 
@@ -441,7 +405,7 @@ class Mlp:
         n = self.nparams
         out = self.new_params() if out is None else out
         st = OwlqnStats()
-        _check_rc(lib().lbf_mlp_l1_pseudo_grad(self.h, ptr(x, numel=n), ptr(g, numel=n), float(l1), int(bool(l1_bias)),
+        check(lib().lbf_mlp_l1_pseudo_grad(self.h, ptr(x, numel=n), ptr(g, numel=n), float(l1), int(bool(l1_bias)),
                                                ptr(out, numel=n), C.byref(st)), "lbf_mlp_l1_pseudo_grad")
         return out, {k: getattr(st, k) for k, _ in OwlqnStats._fields_}
 
@@ -453,7 +417,7 @@ class Mlp:
         n = self.nparams
         out = self.new_params() if out is None else out
         l1t, ww, dec, zeros = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0), C.c_longlong(0)
-        _check_rc(lib().lbf_mlp_l1_trial(self.h, ptr(x, numel=n), ptr(d, numel=n), ptr(pg, numel=n), float(l1),
+        check(lib().lbf_mlp_l1_trial(self.h, ptr(x, numel=n), ptr(d, numel=n), ptr(pg, numel=n), float(l1),
                                          int(bool(l1_bias)), float(alpha), ptr(out, numel=n), C.byref(l1t),
                                          C.byref(ww), C.byref(dec), C.byref(zeros)), "lbf_mlp_l1_trial")
         return out, {"l1_term": l1t.value, "ww": ww.value, "dec": dec.value, "zeros": zeros.value}
@@ -469,15 +433,7 @@ class Mlp:
                idx: Optional[torch.Tensor] = None, inv_scale: Optional[float] = None, l2: float = 0.0,
                eps: float = 1e-4, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """finite_difference_hvp_batch (s_lbfgs.hpp:88-101), the S-LBFGS curvature pair's y."""
-        B = int(idx.numel()) if idx is not None else int(X.shape[0])
-        if inv_scale is None:
-            inv_scale = 1.0 / max(B, 1)
-        out = self.new_params() if out is None else out
-        self._check_data(X, Y)
-        n = self.nparams
-        check(lib().lbf_mlp_fd_hvp(self.h, ptr(params, numel=n), ptr(v, numel=n), ptr(X), ptr(Y),
-                                   ptr(idx, torch.int32), B, inv_scale, l2, eps, ptr(out, numel=n)), "lbf_mlp_fd_hvp")
-        return out
+        return self._product("lbf_mlp_fd_hvp", params, v, X, Y, idx, inv_scale, l2, out, eps)
 
     def __del__(self):
         try:
@@ -517,28 +473,97 @@ class History:
                     accepted=self.accepted[:n].copy())
 
 
-def lbfgs_params(line_search: str = "wolfe", **kw) -> LbfgsParams:
-    p = LbfgsParams()
-    lib().lbf_lbfgs_default_params(C.byref(p), LS_ARMIJO if line_search == "armijo" else LS_WOLFE)
+def _params(what, struct, defaults, kw, reserved=(), aliases=(), ints=()):
+    """The parameter struct of a solver: `struct` with the library's defaults (defaults(pointer)) and the fields that
+    kw names; a None keeps the default. reserved: the fields the solve function owns (trace pointers and capacities);
+    aliases: {keyword: field}; ints: fields that take a bool. An unknown keyword raises LbfError naming the known
+    ones, before the library is touched: a ctypes Structure would take any attribute and ignore it."""
+    aliases = dict(aliases)
+    settable = {k for k, _ in struct._fields_} - set(reserved)
+    for k in kw:
+        if k not in settable and k not in aliases:
+            known = ", ".join(sorted(settable | set(aliases)))
+            raise LbfError(f"{what}: unknown parameter {k!r} (known: {known})")
+    p = struct()
+    defaults(C.byref(p))
     for k, v in kw.items():
         if v is not None:
-            setattr(p, k, v)
+            k = aliases.get(k, k)
+            setattr(p, k, int(v) if k in ints else v)
     return p
 
 
+def lbfgs_params(line_search: str = "wolfe", **kw) -> LbfgsParams:
+    """lbf_lbfgs_params with the defaults of the line search ("wolfe" or "armijo") and the given fields (m, max_iters,
+    tol, max_line_iters, c1, c2, rho). An unknown keyword raises LbfError, here and in the builders below."""
+    ls = LS_ARMIJO if line_search == "armijo" else LS_WOLFE
+    return _params("lbfgs_params", LbfgsParams, lambda p: lib().lbf_lbfgs_default_params(p, ls), kw,
+                   reserved=("line_search",))
+
+
 def slbfgs_params(**kw) -> SlbfgsParams:
-    p = SlbfgsParams()
-    lib().lbf_slbfgs_default_params(C.byref(p))
+    """lbf_slbfgs_params with the library's defaults and the given fields (max_epochs, tol, M, L, b, b_H, step, reg or
+    lam, seed, fd_eps, hvp_exact, dp_mode); the pair trace is slbfgs_solve's."""
     if isinstance(kw.get("dp_mode"), str):
         kw["dp_mode"] = {"replicated": SLBFGS_DP_REPLICATED, "sliced": SLBFGS_DP_SLICED}[kw["dp_mode"]]
     if isinstance(kw.get("hvp_exact"), str):  # "fd", "exact" or "gauss_newton" (LBF_HVP_*); an int passes through
         if kw["hvp_exact"] not in HVP_MODES:
             raise LbfError(f"unknown curvature {kw['hvp_exact']!r}: expected one of {sorted(HVP_MODES)}")
         kw["hvp_exact"] = HVP_MODES[kw["hvp_exact"]]
-    for k, v in kw.items():
-        if v is not None:
-            setattr(p, "reg" if k == "lam" else k, v)
-    return p
+    return _params("slbfgs_params", SlbfgsParams, lambda p: lib().lbf_slbfgs_default_params(p), kw,
+                   reserved=("pair_trace", "pair_trace_cap"), aliases={"lam": "reg"})
+
+
+def gd_params(**kw) -> GdParams:
+    """lbf_gd_params with the library's defaults and the given fields (lr, momentum, max_iters, tol)."""
+    return _params("gd_params", GdParams, lambda p: lib().lbf_gd_default_params(p), kw)
+
+
+def sgd_params(**kw) -> SgdParams:
+    """lbf_sgd_params with the library's defaults and the given fields (lr, momentum, batch, decay_rate, decay_step,
+    max_epochs, tol)."""
+    return _params("sgd_params", SgdParams, lambda p: lib().lbf_sgd_default_params(p), kw)
+
+
+def _pair_trace(p: SlbfgsParams, cap: int):
+    """Points p at a new curvature-pair trace of `cap` rows (NaN until written); None for cap <= 0."""
+    if cap <= 0:
+        return None
+    trace = np.full((int(cap), 8), np.nan)
+    p.pair_trace = trace.ctypes.data_as(C.POINTER(C.c_double))
+    p.pair_trace_cap = int(cap)
+    return trace
+
+
+class _Run:
+    """What LbfgsRun, SlbfgsRun and AdamRun share: the record, the solve info, the handle from lbf_*_begin, iterate
+    and close. _keep holds the tensors the solver reads and writes for as long as the handle lives."""
+    _name = None   # "lbf_lbfgs": the prefix of _begin / _iterate / _end
+    h = None
+
+    def _begin(self, record_cap, keep, *args):
+        self.hist = History(record_cap)
+        self.info = SolveInfo()
+        self._keep = keep
+        h = C.c_void_p()
+        check(getattr(lib(), self._name + "_begin")(*args, C.byref(h)), self._name + "_begin")
+        self.h = h
+
+    def iterate(self, iters: int, *extra):
+        check(getattr(lib(), self._name + "_iterate")(self.h, int(iters), C.byref(self.hist.rec), C.byref(self.info),
+                                                      *extra), self._name + "_iterate")
+        return self.info
+
+    def close(self):
+        if self.h:
+            getattr(lib(), self._name + "_end")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def lbfgs_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, n_global: Optional[int] = None,
@@ -589,35 +614,15 @@ def lbfgs_solve_fn(ctx: Context, params: torch.Tensor, fn, line_search: str = "w
     return hist.as_dict(), info
 
 
-class LbfgsRun:
+class LbfgsRun(_Run):
     """Stateful L-BFGS (begin / iterate / end) used by the benchmark."""
+    _name = "lbf_lbfgs"
 
     def __init__(self, net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor,
                  n_global: Optional[int] = None, line_search: str = "wolfe", record_cap: int = 100000, **kw):
         self.p = lbfgs_params(line_search, **kw)
-        self.hist = History(record_cap)
-        self.info = SolveInfo()
-        self._keep = (net, params, X, Y)
-        h = C.c_void_p()
-        check(lib().lbf_lbfgs_begin(net.h, C.byref(self.p), ptr(params), ptr(X), ptr(Y), int(X.shape[0]),
-                                    int(n_global or X.shape[0]), C.byref(h)), "lbf_lbfgs_begin")
-        self.h = h
-
-    def iterate(self, iters: int):
-        check(lib().lbf_lbfgs_iterate(self.h, iters, C.byref(self.hist.rec), C.byref(self.info)),
-              "lbf_lbfgs_iterate")
-        return self.info
-
-    def close(self):
-        if self.h:
-            lib().lbf_lbfgs_end(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._begin(record_cap, (net, params, X, Y), net.h, C.byref(self.p), ptr(params), ptr(X), ptr(Y),
+                    int(X.shape[0]), int(n_global or X.shape[0]))
 
 
 def slbfgs_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, pair_trace: int = 0, **kw):
@@ -626,11 +631,7 @@ def slbfgs_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tenso
     to that many curvature-pair candidates (diagnostics, synchronous) into hist["pairs"]: rows of (epoch, t,
     y.s, s.s, y.y, accepted, live pairs, 0)."""
     p = slbfgs_params(**kw)
-    trace = None
-    if pair_trace > 0:
-        trace = np.full((int(pair_trace), 8), np.nan)
-        p.pair_trace = trace.ctypes.data_as(C.POINTER(C.c_double))
-        p.pair_trace_cap = int(pair_trace)
+    trace = _pair_trace(p, pair_trace)
     hist = History(p.max_epochs)
     info = SolveInfo()
     check(lib().lbf_slbfgs_solve(net.h, C.byref(p), ptr(params), ptr(X), ptr(Y), int(X.shape[0]),
@@ -641,31 +642,18 @@ def slbfgs_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tenso
     return out, info
 
 
-class SlbfgsRun:
+class SlbfgsRun(_Run):
     """Stateful S-LBFGS (begin / iterate / end) used by the benchmark: the epochs of one solve across several
     iterate() calls (the breakdown, warmup and timed epochs), bitwise one lbf_slbfgs_solve."""
+    _name = "lbf_slbfgs"
 
     def __init__(self, net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, record_cap: int = 100000,
                  pair_trace: int = 0, **kw):
         self.p = slbfgs_params(**kw)
         self.p.max_epochs = max(int(self.p.max_epochs), 1 << 30)
-        self.trace = None
-        if pair_trace > 0:  # diagnostics: rows as slbfgs_solve's hist["pairs"], and pair0()
-            self.trace = np.full((int(pair_trace), 8), np.nan)
-            self.p.pair_trace = self.trace.ctypes.data_as(C.POINTER(C.c_double))
-            self.p.pair_trace_cap = int(pair_trace)
-        self.hist = History(record_cap)
-        self.info = SolveInfo()
-        self._keep = (net, params, X, Y)
-        h = C.c_void_p()
-        check(lib().lbf_slbfgs_begin(net.h, C.byref(self.p), ptr(params), ptr(X), ptr(Y), int(X.shape[0]),
-                                     C.byref(h)), "lbf_slbfgs_begin")
-        self.h = h
-
-    def iterate(self, epochs: int):
-        check(lib().lbf_slbfgs_iterate(self.h, epochs, C.byref(self.hist.rec), C.byref(self.info)),
-              "lbf_slbfgs_iterate")
-        return self.info
+        self.trace = _pair_trace(self.p, pair_trace)   # diagnostics: rows as slbfgs_solve's hist["pairs"], and pair0()
+        self._begin(record_cap, (net, params, X, Y), net.h, C.byref(self.p), ptr(params), ptr(X), ptr(Y),
+                    int(X.shape[0]))
 
     def pairs(self):
         return None if self.trace is None else self.trace[~np.isnan(self.trace[:, 0])]
@@ -693,26 +681,11 @@ class SlbfgsRun:
         check(lib().lbf_slbfgs_pair_io(self.h, int(cap), ptr(rec), ptr(force)), "lbf_slbfgs_pair_io")
         return rec
 
-    def close(self):
-        if self.h:
-            lib().lbf_slbfgs_end(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def gd_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, n_global: Optional[int] = None,
              **kw):
-    """CudaGD::solve (src/cuda/gd.cuh:38-106); params updated in place. kw: lr, momentum, max_iters, tol."""
-    p = GdParams()
-    lib().lbf_gd_default_params(C.byref(p))
-    for k, v in kw.items():
-        if v is not None:
-            setattr(p, k, v)
+    """CudaGD::solve (src/cuda/gd.cuh:38-106); params updated in place. kw: see gd_params."""
+    p = gd_params(**kw)
     hist = History(max(p.max_iters, 1))
     info = SolveInfo()
     n_local = int(X.shape[0])
@@ -725,15 +698,8 @@ def hf_params(**kw) -> HfParams:
     """lbf_hf_params with the library's defaults and the given fields (max_iters, tol, cg_iters, cg_rtol, cg_check,
     damping0, damp_up, damp_down, ratio_lo, ratio_hi, c1, rho, max_line_iters, curv_rows); the trace pointers are
     hf_solve's. An unknown keyword raises LbfError."""
-    p = HfParams()
-    lib().lbf_hf_default_params(C.byref(p))
-    settable = {k for k, _ in HfParams._fields_} - {"damping_trace", "ratio_trace", "cg_trace", "trace_cap"}
-    for k, v in kw.items():
-        if k not in settable:
-            raise LbfError(f"hf_params: unknown parameter {k!r} (known: {', '.join(sorted(settable))})")
-        if v is not None:
-            setattr(p, k, v)
-    return p
+    return _params("hf_params", HfParams, lambda p: lib().lbf_hf_default_params(p), kw,
+                   reserved=("damping_trace", "ratio_trace", "cg_trace", "trace_cap"))
 
 
 def hf_precond(precond: str = "none", exponent: float = 0.75, refresh: int = 1) -> HfPrecond:
@@ -783,15 +749,8 @@ def hf_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, n
 def owlqn_params(**kw) -> OwlqnParams:
     """lbf_owlqn_params with the library's defaults and the given fields (m, max_iters, tol, l1, l1_bias, c1, rho,
     max_line_iters); the trace pointer is owlqn_solve's. An unknown keyword raises LbfError."""
-    p = OwlqnParams()
-    lib().lbf_owlqn_default_params(C.byref(p))
-    settable = {k for k, _ in OwlqnParams._fields_} - {"zeros_trace", "trace_cap"}
-    for k, v in kw.items():
-        if k not in settable:
-            raise LbfError(f"owlqn_params: unknown parameter {k!r} (known: {', '.join(sorted(settable))})")
-        if v is not None:
-            setattr(p, k, int(v) if k == "l1_bias" else v)
-    return p
+    return _params("owlqn_params", OwlqnParams, lambda p: lib().lbf_owlqn_default_params(p), kw,
+                   reserved=("zeros_trace", "trace_cap"), ints=("l1_bias",))
 
 
 def owlqn_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, n_global: Optional[int] = None,
@@ -823,15 +782,8 @@ def adam_params(**kw) -> AdamParams:
     """lbf_adam_params with the library's defaults and the given fields (lr, beta1, beta2, eps, weight_decay,
     clip_norm, batch, shuffle, seed, decay_rate, decay_step, max_epochs, tol); the trace pointer is adam_solve's.
     An unknown keyword raises LbfError."""
-    p = AdamParams()
-    lib().lbf_adam_default_params(C.byref(p))
-    settable = {k for k, _ in AdamParams._fields_} - {"loss_trace", "trace_cap"}
-    for k, v in kw.items():
-        if k not in settable:
-            raise LbfError(f"adam_params: unknown parameter {k!r} (known: {', '.join(sorted(settable))})")
-        if v is not None:
-            setattr(p, k, int(v) if k == "shuffle" else v)
-    return p
+    return _params("adam_params", AdamParams, lambda p: lib().lbf_adam_default_params(p), kw,
+                   reserved=("loss_trace", "trace_cap"), ints=("shuffle",))
 
 
 def adam_coefs(p: AdamParams, lr_now: float, t: int) -> AdamCoef:
@@ -882,9 +834,10 @@ class _Epochs:
         self.iterations = int(iterations)
 
 
-class AdamRun:
+class AdamRun(_Run):
     """Stateful Adam (lbf_adam_begin / iterate / end): the epochs of one solve across several iterate() calls,
     bitwise one adam_solve. max_epochs bounds the loss trace only; iterate() decides how many epochs run."""
+    _name = "lbf_adam"
 
     def __init__(self, net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, record_cap: int = 100000,
                  **kw):
@@ -892,45 +845,23 @@ class AdamRun:
         net._check_data(X, Y)
         N = int(X.shape[0])
         self.trace = _adam_trace(self.p, N, self.p.max_epochs)
-        self.hist = History(record_cap)
-        self.info = SolveInfo()
         self.epochs = 0
-        self._keep = (net, params, X, Y)
-        h = C.c_void_p()
-        check(lib().lbf_adam_begin(net.h, C.byref(self.p), ptr(params, numel=net.nparams), ptr(X), ptr(Y), N,
-                                   C.byref(h)), "lbf_adam_begin")
-        self.h = h
+        self._begin(record_cap, (net, params, X, Y), net.h, C.byref(self.p), ptr(params, numel=net.nparams), ptr(X),
+                    ptr(Y), N)
 
     def iterate(self, epochs: int):
         done = C.c_int(0)
-        check(lib().lbf_adam_iterate(self.h, int(epochs), C.byref(self.hist.rec), C.byref(self.info), C.byref(done)),
-              "lbf_adam_iterate")
+        super().iterate(epochs, C.byref(done))
         self.epochs = int(done.value)
         return _Epochs(self.epochs)
 
     def loss_trace(self):
         return self.trace[~np.isnan(self.trace)]
 
-    def close(self):
-        if self.h:
-            lib().lbf_adam_end(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
 def sgd_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, record: bool = True, **kw):
-    """CudaSGD::solve (src/cuda/sgd.cuh:50-153). kw: lr, momentum, batch, decay_rate, decay_step,
-    max_epochs, tol. record=False runs without the recorder (no full-batch evaluations)."""
-    p = SgdParams()
-    lib().lbf_sgd_default_params(C.byref(p))
-    for k, v in kw.items():
-        if v is not None:
-            setattr(p, k, v)
+    """CudaSGD::solve (src/cuda/sgd.cuh:50-153). kw: see sgd_params. record=False runs without the recorder (no
+    full-batch evaluations)."""
+    p = sgd_params(**kw)
     hist = History(p.max_epochs + 1)
     info = SolveInfo()
     check(lib().lbf_sgd_solve(net.h, C.byref(p), ptr(params), ptr(X), ptr(Y), int(X.shape[0]),

@@ -175,6 +175,17 @@ class UnifiedOptimizer:
         raise NotImplementedError
 
 
+def _recorded(optimizer: UnifiedOptimizer, hist, info) -> IterationRecorder:
+    """What every optimize() ends with: the solver's history dict and solve info kept as optimizer.history and
+    optimizer.info, and the history's loss, gradient norm and time as the IterationRecorder that train() writes."""
+    rec = IterationRecorder()
+    for i in range(len(hist["loss"])):
+        rec.record(i, float(hist["loss"][i]), float(hist["grad_norm"][i]), float(hist["time_ms"][i]))
+    optimizer.info = info
+    optimizer.history = hist
+    return rec
+
+
 class EarlyStopper:
     """Decides when validation-monitored training stops: after `patience` evaluations in a row that bring no
     strict improvement of the monitored value ("loss": lower is better, "accuracy": higher is better). A tie is
@@ -278,13 +289,8 @@ def _monitored_run(optimizer: "UnifiedOptimizer", net: _DeviceNet, data: "_Devic
     optimizer.validation = validation
     optimizer.best_iteration = stopper.best_iteration
     optimizer.stopped_early = bool(stopper.patience > 0 and stopper.stale >= stopper.patience)
-    hist = run.hist.as_dict()
-    rec = IterationRecorder()
-    for i in range(len(hist["loss"])):
-        rec.record(i, float(hist["loss"][i]), float(hist["grad_norm"][i]), float(hist["time_ms"][i]))
+    rec = _recorded(optimizer, run.hist.as_dict(), run.info)
     rec.validation = list(validation)
-    optimizer.info = run.info
-    optimizer.history = hist
     return rec
 
 
@@ -303,12 +309,7 @@ class UnifiedLBFGS(UnifiedOptimizer):
         hist, info = engine.lbfgs_solve(net.mlp, net.params, data.x, data.y, n_global=data.n_global,
                                         line_search=config.line_search, m=config.m_param if config.m_param > 0 else 10,
                                         max_iters=config.max_iters, tol=config.tolerance)
-        rec = IterationRecorder()
-        for i in range(len(hist["loss"])):
-            rec.record(i, float(hist["loss"][i]), float(hist["grad_norm"][i]), float(hist["time_ms"][i]))
-        self.info = info
-        self.history = hist
-        return rec
+        return _recorded(self, hist, info)
 
 
 class UnifiedSLBFGS(UnifiedOptimizer):
@@ -329,12 +330,7 @@ class UnifiedSLBFGS(UnifiedOptimizer):
                                          tol=config.tolerance, M=config.m_param, L=config.L_param,
                                          b=config.batch_size, b_H=b_H, step=config.learning_rate, lam=1e-4,
                                          seed=123, hvp_exact=config.curvature)
-        rec = IterationRecorder()
-        for i in range(len(hist["loss"])):
-            rec.record(i, float(hist["loss"][i]), float(hist["grad_norm"][i]), float(hist["time_ms"][i]))
-        self.info = info
-        self.history = hist
-        return rec
+        return _recorded(self, hist, info)
 
 
 class UnifiedGD(UnifiedOptimizer):
@@ -347,12 +343,7 @@ class UnifiedGD(UnifiedOptimizer):
         hist, info = engine.gd_solve(net.mlp, net.params, data.x, data.y, n_global=data.n_global,
                                      lr=config.learning_rate, momentum=config.momentum, max_iters=config.max_iters,
                                      tol=config.tolerance)
-        rec = IterationRecorder()
-        for i in range(len(hist["loss"])):
-            rec.record(i, float(hist["loss"][i]), float(hist["grad_norm"][i]), float(hist["time_ms"][i]))
-        self.info = info
-        self.history = hist
-        return rec
+        return _recorded(self, hist, info)
 
 
 class UnifiedHF(UnifiedOptimizer):
@@ -371,13 +362,8 @@ class UnifiedHF(UnifiedOptimizer):
                                              max_iters=config.max_iters, tol=config.tolerance,
                                              cg_iters=config.cg_iters, cg_rtol=config.cg_rtol,
                                              damping0=config.damping, curv_rows=config.curv_rows)
-        rec = IterationRecorder()
-        for i in range(len(hist["loss"])):
-            rec.record(i, float(hist["loss"][i]), float(hist["grad_norm"][i]), float(hist["time_ms"][i]))
-        self.info = info
-        self.history = hist
         self.traces = traces
-        return rec
+        return _recorded(self, hist, info)
 
 
 class UnifiedOWLQN(UnifiedOptimizer):
@@ -391,13 +377,8 @@ class UnifiedOWLQN(UnifiedOptimizer):
         hist, info, stats = engine.owlqn_solve(net.mlp, net.params, data.x, data.y, n_global=data.n_global,
                                                m=config.m_param, max_iters=config.max_iters, tol=config.tolerance,
                                                l1=config.l1)
-        rec = IterationRecorder()
-        for i in range(len(hist["loss"])):
-            rec.record(i, float(hist["loss"][i]), float(hist["grad_norm"][i]), float(hist["time_ms"][i]))
-        self.info = info
-        self.history = hist
         self.stats = stats
-        return rec
+        return _recorded(self, hist, info)
 
 
 class UnifiedSGD(UnifiedOptimizer):
@@ -411,12 +392,7 @@ class UnifiedSGD(UnifiedOptimizer):
         hist, info = engine.sgd_solve(net.mlp, net.params, data.x_full, data.y_full, lr=config.learning_rate,
                                       momentum=config.momentum, batch=config.batch_size, max_epochs=config.max_iters,
                                       decay_rate=config.lr_decay, decay_step=config.lr_decay_rate)
-        rec = IterationRecorder()
-        for i in range(len(hist["loss"])):
-            rec.record(i, float(hist["loss"][i]), float(hist["grad_norm"][i]), float(hist["time_ms"][i]))
-        self.info = info
-        self.history = hist
-        return rec
+        return _recorded(self, hist, info)
 
 
 class UnifiedAdam(UnifiedOptimizer):
@@ -444,13 +420,8 @@ class UnifiedAdam(UnifiedOptimizer):
             self.trace = run.loss_trace()
             return rec
         hist, info, trace = engine.adam_solve(net.mlp, net.params, data.x_full, data.y_full, **self._kw(config))
-        rec = IterationRecorder()
-        for i in range(len(hist["loss"])):
-            rec.record(i, float(hist["loss"][i]), float(hist["grad_norm"][i]), float(hist["time_ms"][i]))
-        self.info = info
-        self.history = hist
         self.trace = trace
-        return rec
+        return _recorded(self, hist, info)
 
 
 class _DeviceData:

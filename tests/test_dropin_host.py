@@ -4,6 +4,9 @@ functions the header calls that records every argument. The harness checks each 
 the header fills (Unified{LBFGS,SLBFGS,GD,SGD,HF,OWLQN}_HIP, HipLBFGS, HipHF, HipOWLQN), the launcher's call
 order (l2, re-draw, solve, scan), the host scan of evaluate() against long double, the metrics rescaling, the
 recorder, the history CSV, HostMatrix, DeviceBuffer and MNISTLoader (over the engine's own csrc/idx.cpp).
+That program links without the entry points fake_lbf_abi.cpp leaves out (the link proof of DESIGN.md §17).
+tests/host/dropin_harness_v2.cpp does the same for the classes that call them (HipNetwork::gradSq,
+HipHFPreconditioned, HipAdam, UnifiedHFPreconditioned_HIP, UnifiedAdam_HIP), linked with fake_lbf_abi_v2.cpp as well.
 
 Built with g++ twice, plain and under AddressSanitizer + UndefinedBehaviorSanitizer, and run as a process of
 its own (the pattern of test_host_sanitizers.py). No GPU, nothing loaded into Python.
@@ -28,14 +31,26 @@ pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 FLAGS = {"plain": [], "asan_ubsan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]}
 
 
-@pytest.fixture(scope="module", params=list(FLAGS))
-def harness(request, tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("dropin_" + request.param) / "dropin_harness")
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-O1", "-g", *FLAGS[request.param], *INC, *SRC, "-o", exe],
+SRC_V2 = [os.path.join(HOST, "dropin_harness_v2.cpp"), os.path.join(HOST, "fake_lbf_abi_v2.cpp"), *SRC[1:]]
+
+
+def build(tmp_path_factory, flavour, name, src):
+    exe = str(tmp_path_factory.mktemp(name + "_" + flavour) / name)
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-O1", "-g", *FLAGS[flavour], *INC, *src, "-o", exe],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-4000:]
     assert "warning" not in r.stderr, r.stderr[-4000:]
     return exe
+
+
+@pytest.fixture(scope="module", params=list(FLAGS))
+def harness(request, tmp_path_factory):
+    return build(tmp_path_factory, request.param, "dropin_harness", SRC)
+
+
+@pytest.fixture(scope="module", params=list(FLAGS))
+def harness_v2(request, tmp_path_factory):
+    return build(tmp_path_factory, request.param, "dropin_harness_v2", SRC_V2)
 
 
 def run(exe, *args):
@@ -59,3 +74,11 @@ def test_negative_l2_before_bind_aborts(harness, tmp_path):
     assert r.returncode == -signal.SIGABRT, (r.returncode, r.stdout[-1000:], r.stderr[-2000:])
     assert "HIP engine error: lbf_mlp_set_l2" in r.stderr
     assert "setL2(-1) returned" not in r.stdout
+
+
+def test_later_classes_against_both_recording_abis(harness_v2, tmp_path):
+    r = run(harness_v2, tmp_path)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    assert "dropin harness v2 ok" in r.stdout
+    assert (tmp_path / "v2name_history.csv").exists()
