@@ -34,6 +34,10 @@ extern "C" {
 #define LBF_ACT_TANH 1
 #define LBF_ACT_RELU 2
 #define LBF_ACT_SIGMOID 3
+/* Rectifiers with curvature (an extension: the reference has the four above). Constants are fixed. */
+#define LBF_ACT_LEAKY_RELU 4 /* x > 0 ? x : 0.01 x                          */
+#define LBF_ACT_ELU 5        /* x > 0 ? x : expm1(x)             (alpha 1)  */
+#define LBF_ACT_SOFTPLUS 6   /* max(x, 0) + log1p(exp(-|x|)) = log(1 + e^x) */
 
 /* Line-search / two-loop policies.
  * WOLFE  = CPU semantics: src/minimizer/lbfgs.hpp:38-139 + full_batch_minimizer.hpp:126-157.
@@ -87,7 +91,23 @@ int lbf_comm_rank(lbf_ctx *ctx, int *rank, int *nranks);
 int lbf_allreduce_sum(lbf_ctx *ctx, float *d_buf, size_t count);
 
 /* ---- dense MLP --------------------------------------------------------------------------------
- * Replaces CudaNetwork (src/cuda/network.cuh:21-158) / CudaDenseLayer (src/cuda/layer.cuh). */
+ * Replaces CudaNetwork (src/cuda/network.cuh:21-158) / CudaDenseLayer (src/cuda/layer.cuh).
+ * acts[l] is an LBF_ACT_* id, 0..6 (else LBF_ERR_INVALID). Only the post-activation values y are stored, and
+ * act' and act'' are taken through them:
+ *   linear      y = x                               act' = 1                    act'' = 0
+ *   tanh        y = tanh x                          act' = 1 - y^2              act'' = -2 y (1 - y^2)
+ *   relu        y = max(x, 0)                       act' = [y > 0]              act'' = 0
+ *   sigmoid     y = 1 / (1 + e^-x)                  act' = y (1 - y)            act'' = y (1 - y) (1 - 2 y)
+ *   leaky_relu  y = x > 0 ? x : 0.01 x              act' = y > 0 ? 1 : 0.01     act'' = 0
+ *   elu         y = x > 0 ? x : expm1(x)            act' = y > 0 ? 1 : y + 1    act'' = y > 0 ? 0 : y + 1
+ *   softplus    y = max(x, 0) + log1p(e^-|x|)       act' = -expm1(-y)           act'' = e^-y (-expm1(-y))
+ * The slope 0.01 and alpha 1 are fixed (torch's defaults); there is no per-layer parameter. The three new ones
+ * are strictly increasing, so y determines x and the identities are exact. Any of them may sit on the output
+ * layer under LBF_LOSS_MSE; LBF_LOSS_SOFTMAX_XENT keeps its linear last layer. The fused output-layer kernels carry
+ * the first four only: with one of the three on the last or the last hidden layer, the output layer runs as a forward
+ * GEMM, the loss kernel and a backward GEMM (same results, one more pass over the last activations).
+ * lbf_mlp_init_params and lbf_init_params_host give relu, leaky_relu, elu and softplus the same sqrt(2) gain in
+ * both init modes, so exchanging one for another keeps a seed's start point bit for bit. */
 int lbf_mlp_create(lbf_ctx *ctx, int nlayers, const int *dims /* nlayers+1 */, const int *acts /* nlayers */,
                    lbf_mlp **out);
 int lbf_mlp_destroy(lbf_mlp *net);

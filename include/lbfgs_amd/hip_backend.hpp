@@ -58,6 +58,10 @@ struct Linear { static constexpr int id = LBF_ACT_LINEAR; };
 struct Tanh { static constexpr int id = LBF_ACT_TANH; };
 struct ReLU { static constexpr int id = LBF_ACT_RELU; };
 struct Sigmoid { static constexpr int id = LBF_ACT_SIGMOID; };
+/// Rectifiers with curvature (an extension; formulas and fixed constants: lbf_mlp_create in lbfgs_amd.h).
+struct LeakyReLU { static constexpr int id = LBF_ACT_LEAKY_RELU; };
+struct ELU { static constexpr int id = LBF_ACT_ELU; };
+struct Softplus { static constexpr int id = LBF_ACT_SOFTPLUS; };
 
 /// The loss the network's evaluations and every solver on it minimise (lbf_mlp_set_loss; an extension: the
 /// reference has the squared error only). SoftmaxCrossEntropy takes the outputs of a Linear last layer as logits.

@@ -20,7 +20,8 @@ SLBFGS_DP_REPLICATED, SLBFGS_DP_SLICED = 0, 1
 HVP_MODES = {"fd": 0, "exact": 1, "gauss_newton": 2}  # LBF_HVP_FD, LBF_HVP_EXACT, LBF_HVP_GAUSS_NEWTON
 LS_WOLFE, LS_ARMIJO = 0, 1
 INIT_CPU, INIT_CUDA = 0, 1
-ACTS = {"linear": 0, "tanh": 1, "relu": 2, "sigmoid": 3}
+# LBF_ACT_* of include/lbfgs_amd.h (leaky_relu: slope 0.01, elu: alpha 1; fixed, as torch's defaults)
+ACTS = {"linear": 0, "tanh": 1, "relu": 2, "sigmoid": 3, "leaky_relu": 4, "elu": 5, "softplus": 6}
 LOSSES = {"mse": 0, "softmax_xent": 1}  # LBF_LOSS_MSE, LBF_LOSS_SOFTMAX_XENT
 PRECONDS = {"none": 0, "grad_sq": 1}  # LBF_PRECOND_NONE, LBF_PRECOND_GRAD_SQ
 
@@ -238,6 +239,19 @@ def lib():
         raise LbfError(f"{LIB_PATH} implements ABI {L.lbf_abi_version()}, this binding needs {ABI_VERSION}: rebuild it")
     _lib = L
     return L
+
+
+def act_ids(acts) -> list:
+    """Activation names (or LBF_ACT_* ids, which lbf_mlp_create range-checks) as ids."""
+    out = []
+    for a in acts:
+        if isinstance(a, str):
+            if a not in ACTS:
+                raise LbfError(f"unknown activation {a!r} (known: {', '.join(sorted(ACTS))})")
+            out.append(ACTS[a])
+        else:
+            out.append(int(a))
+    return out
 
 
 def check_precond(name) -> int:

@@ -188,6 +188,10 @@ int lbf_allreduce_sum(lbf_ctx *ctx, float *d_buf, size_t count) {
 int lbf_mlp_create(lbf_ctx *ctx, int nlayers, const int *dims, const int *acts, lbf_mlp **out) {
   return guard([&] {
     LBF_REQUIRE(ctx && dims && acts && out, "null argument");
+    static_assert(LBF_ACT_LINEAR == ACT_LINEAR && LBF_ACT_TANH == ACT_TANH && LBF_ACT_RELU == ACT_RELU &&
+                      LBF_ACT_SIGMOID == ACT_SIGMOID && LBF_ACT_LEAKY_RELU == ACT_LEAKY_RELU &&
+                      LBF_ACT_ELU == ACT_ELU && LBF_ACT_SOFTPLUS == ACT_SOFTPLUS && ACT_COUNT == 7,
+                  "activation codes");
     ctx->c.set_device();
     auto m = std::make_unique<lbf_mlp>();
     m->ctx = ctx;

@@ -25,6 +25,15 @@
 
 namespace lbf {
 
+// Instances with all seven activation bodies (act.hpp), picked by gemm() when a rectifier sits in the epilogue or
+// in the A-from-slabs prologue. Compile-time constants of their own, as EPI_HEAD_XENT is, so the instances of
+// EPI_FWD, EPI_DX and EPI_STORE are the four-body code they were.
+enum : int { EPI_FWD_X = 5, EPI_DX_X = 6, EPI_STORE_X = 7 };
+constexpr int epi_base(int epi) {
+  return epi == EPI_FWD_X ? int(EPI_FWD) : epi == EPI_DX_X ? int(EPI_DX) : epi == EPI_STORE_X ? int(EPI_STORE) : epi;
+}
+constexpr bool epi_xact(int epi) { return epi >= EPI_FWD_X; }
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct GemmK {
@@ -386,7 +395,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmK &g, f32x16 (&acc)[TM][
         const int r = rows_tile + e / hs.Hp, c = e % hs.Hp;
         hs.As[r * hs.LDA + c] = 0.0f;
       }
-      with_act(g.act, [&](auto AC) __attribute__((always_inline)) {
+      with_act4(g.act, [&](auto AC) __attribute__((always_inline)) {
         constexpr int A = decltype(AC)::value;
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm)
@@ -430,23 +439,23 @@ __device__ __forceinline__ void gemm_epilogue(const GemmK &g, f32x16 (&acc)[TM][
   }
   if (KW > 1 && kgrp != 0) return; // group 0 holds the sums
   // Epilogue: lanes 0-31 own consecutive columns -> each register row is a 128-B coalesced store.
-  float *C = g.C + (EPI == EPI_STORE ? (long long)zsplit * g.slab_stride : 0LL);
+  constexpr int EB = epi_base(EPI);
+  float *C = g.C + (EB == EPI_STORE ? (long long)zsplit * g.slab_stride : 0LL);
   // EPI_DX's act' operand (the previous layer's activations) is loaded for the whole (tm, tn) block before
   // the first use, from clamped addresses: a load-use-store per element made every element a dependent
   // memory round trip (64 per lane at 128 x 128; the cfg-3 dX GEMM spent most of its 35 us there).
-  with_act(EPI == EPI_FWD ? g.act : (EPI == EPI_DX ? g.aux_act : int(ACT_LINEAR)),
-           [&](auto AC) __attribute__((always_inline)) {
+  auto store = [&](auto AC) __attribute__((always_inline)) {
     constexpr int A = decltype(AC)::value;
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) {
       const int n = n0 + wn * TN * 32 + tn * 32 + li;
       const bool nok = n < g.N;
       float bn = 0.0f;
-      if constexpr (EPI == EPI_FWD) bn = g.bias ? g.bias[nok ? n : 0] : 0.0f;
+      if constexpr (EB == EPI_FWD) bn = g.bias ? g.bias[nok ? n : 0] : 0.0f;
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm) {
         float ax[16];
-        if constexpr (EPI == EPI_DX) {
+        if constexpr (EB == EPI_DX) {
           const int nc = nok ? n : 0;
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
@@ -458,13 +467,16 @@ __device__ __forceinline__ void gemm_epilogue(const GemmK &g, f32x16 (&acc)[TM][
         for (int r = 0; r < 16; ++r) {
           const int m = m0 + wm * TM * 32 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
           float v = acc[tm][tn][r];
-          if constexpr (EPI == EPI_FWD) v = act_c<A>(v + bn);
-          if constexpr (EPI == EPI_DX) v *= dact_c<A>(ax[r]);
+          if constexpr (EB == EPI_FWD) v = act_c<A>(v + bn);
+          if constexpr (EB == EPI_DX) v *= dact_c<A>(ax[r]);
           if (nok && m < g.M) C[(long long)m * g.ldc + n] = v;
         }
       }
     }
-  });
+  };
+  const int ea = EB == EPI_FWD ? g.act : (EB == EPI_DX ? g.aux_act : int(ACT_LINEAR));
+  if constexpr (epi_xact(EPI)) with_act(ea, store);
+  else with_act4(ea, store);
 }
 
 // KW k-groups of 4 waves each (KW = 2: 8 waves, two per SIMD, for tiles too small to fill the chip
@@ -982,7 +994,7 @@ __device__ __forceinline__ void glds_body(const GemmK &g, float *lds, int zsplit
       const f32x4 b4 = *reinterpret_cast<const f32x4 *>(g.a_bias + (ok ? kq : 0));
       f32x4 a4;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) a4[e] = ok ? act_rt(g.a_act, sum[e] + b4[e]) : 0.0f;
+      for (int e = 0; e < 4; ++e) a4[e] = ok ? (epi_xact(EPI) ? act_rt(g.a_act, sum[e] + b4[e]) : act_rt4(g.a_act, sum[e] + b4[e])) : 0.0f;
       *reinterpret_cast<f32x4 *>(lds + (t % NS) * STG + wave * 256 + lane * 4) = a4;
       if (ok && bx == 0) *reinterpret_cast<f32x4 *>(g.a_out + rbase + kq) = a4;
     }
@@ -1294,11 +1306,15 @@ void gemm_group(hipStream_t s, const GemmDesc &d1, const GemmDesc &d2) {
 void gemm(hipStream_t s, const GemmDesc &d) {
   if (d.M <= 0 || d.N <= 0) return;
   if (d.a_slab && !gemm_asum_ok(d)) throw std::runtime_error("gemm: A from slabs not supported for this shape");
+  // a rectifier in the epilogue or in the A-from-slabs prologue: the instance with all seven activation bodies
+  const bool xact = !act_in_heads(d.act) || !act_in_heads(d.aux_act) || (d.a_slab && !act_in_heads(d.a_act));
   if (d.epi == EPI_HEAD) {
     int BM, BN;
     gemm_tile_for(d.N, d.tile, &BM, &BN);
     if (!(d.a_kc && !d.b_kc) || d.N > BN || d.splits > 1 || d.head_out < 1 || d.head_out > headc::HMAX_OUT)
       throw std::runtime_error("gemm: EPI_HEAD needs an unsplit forward GEMM with N <= the tile width");
+    if (!act_in_heads(d.act) || !act_in_heads(d.head_act))
+      throw std::runtime_error("gemm: EPI_HEAD carries the linear, tanh, relu and sigmoid bodies only");
     if (d.head_fold >= 0 &&
         (d.N > 128 || d.head_fold > headc::FOLD_MAX || d.head_fold % 4 || d.head_fold_c0 % 4 || d.lda % 4 ||
          d.head_fold_c0 + d.head_fold != d.K || !aligned16(d.A)))
@@ -1310,10 +1326,17 @@ void gemm(hipStream_t s, const GemmDesc &d) {
     } else {
       dispatch_tile<true, false, EPI_HEAD>(s, d);
     }
-  } else if (d.epi == EPI_FWD && d.a_kc && !d.b_kc) dispatch_tile<true, false, EPI_FWD>(s, d);
-  else if (d.epi == EPI_DX && d.a_kc && d.b_kc) dispatch_tile<true, true, EPI_DX>(s, d);
-  else if (d.epi == EPI_STORE && !d.a_kc && !d.b_kc) dispatch_tile<false, false, EPI_STORE>(s, d);
-  else if (d.epi == EPI_STORE && d.a_kc && !d.b_kc) dispatch_tile<true, false, EPI_STORE>(s, d);
+  } else if (d.epi == EPI_FWD && d.a_kc && !d.b_kc) {
+    if (xact) dispatch_tile<true, false, EPI_FWD_X>(s, d);
+    else dispatch_tile<true, false, EPI_FWD>(s, d);
+  } else if (d.epi == EPI_DX && d.a_kc && d.b_kc) {
+    if (xact) dispatch_tile<true, true, EPI_DX_X>(s, d);
+    else dispatch_tile<true, true, EPI_DX>(s, d);
+  } else if (d.epi == EPI_STORE && !d.a_kc && !d.b_kc) dispatch_tile<false, false, EPI_STORE>(s, d);
+  else if (d.epi == EPI_STORE && d.a_kc && !d.b_kc) {
+    if (xact) dispatch_tile<true, false, EPI_STORE_X>(s, d); // the A-from-slabs prologue applies a_act
+    else dispatch_tile<true, false, EPI_STORE>(s, d);
+  }
   else throw std::runtime_error("gemm: unsupported operand/epilogue combination");
   LBF_KERNEL_CHECK();
 }

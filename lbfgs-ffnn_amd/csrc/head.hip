@@ -300,7 +300,7 @@ __global__ __launch_bounds__(256) void rowhead_kernel(const RowHeadArgs a) {
     KT(43);
     // ---- activations (fwd_reduce_act's arithmetic) ----
     float av[NJ];
-    with_act(a.act_prev, [&](auto AC) __attribute__((always_inline)) {
+    with_act4(a.act_prev, [&](auto AC) __attribute__((always_inline)) {
       constexpr int A = decltype(AC)::value;
 #pragma unroll
       for (int j = 0; j < NJ; ++j) av[j] = cv[j] ? act_c<A>(sum[j] + hb[j]) : 0.0f;
@@ -338,7 +338,7 @@ __global__ __launch_bounds__(256) void rowhead_kernel(const RowHeadArgs a) {
           dz[o] = (dz[o] * rs * ysum - yv[o]) * float(a.inv_scale);
         }
     } else {
-      with_act(a.act_out, [&](auto AC) __attribute__((always_inline)) {
+      with_act4(a.act_out, [&](auto AC) __attribute__((always_inline)) {
         constexpr int A = decltype(AC)::value;
 #pragma unroll
         for (int o = 0; o < OP; ++o) {
@@ -358,7 +358,7 @@ __global__ __launch_bounds__(256) void rowhead_kernel(const RowHeadArgs a) {
     }
     KT(44);
     // ---- delta = (dZ W^T) .* act_prev'(a), [dW ; db] += [a | 1]^T dZ ----
-    with_act(a.act_prev, [&](auto AC) __attribute__((always_inline)) {
+    with_act4(a.act_prev, [&](auto AC) __attribute__((always_inline)) {
       constexpr int A = decltype(AC)::value;
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
@@ -424,6 +424,7 @@ int rowhead_nwg(long long B) { return int(cdiv(std::max(1LL, B), 4LL * rowhead_r
 
 void rowhead(hipStream_t s, const RowHeadArgs &a) {
   LBF_REQUIRE(rowhead_supported(a.H, a.Out) && a.splits >= 1 && a.rpw == rowhead_rpw(a.B), "rowhead: shape");
+  LBF_REQUIRE(act_in_heads(a.act_out) && act_in_heads(a.act_prev), "rowhead: linear, tanh, relu and sigmoid only");
   LBF_REQUIRE(a.loss == LOSS_MSE || (a.loss == LOSS_XENT && a.act_out == ACT_LINEAR && a.Out >= 2),
               "rowhead: the cross-entropy head needs a linear output layer with Out >= 2");
   const size_t shmem = size_t(5) * (a.H + 1) * a.Out * sizeof(float); // 4 wave partials + [W ; b]
@@ -477,6 +478,7 @@ void head_fused(hipStream_t s, const float *A, int H, const float *P, int Out, c
                 double *sse_part, const int *abort, int loss) {
   LBF_REQUIRE(loss == LOSS_MSE || (loss == LOSS_XENT && act_out == ACT_LINEAR && Out >= 2),
               "head: the cross-entropy head needs a linear output layer with Out >= 2");
+  LBF_REQUIRE(act_in_heads(act_out) && act_in_heads(act_prev), "head: linear, tanh, relu and sigmoid only");
   const size_t shmem = size_t(smem_floats(H)) * sizeof(float);
   // once per process, thread-safe (rank threads of an in-process group launch concurrently)
   static const bool attr_set = [] {

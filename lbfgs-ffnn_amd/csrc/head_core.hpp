@@ -289,7 +289,7 @@ __device__ inline void tile(const Smem &s, const TileArgs &a, long long b0, int 
         s.Dz[row * LDZ + dzc] = dz;
       }
     } else {
-      with_act(a.act_out, [&](auto AC) __attribute__((always_inline)) {
+      with_act4(a.act_out, [&](auto AC) __attribute__((always_inline)) {
         constexpr int A = decltype(AC)::value;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -359,7 +359,7 @@ __device__ inline void tile(const Smem &s, const TileArgs &a, long long b0, int 
   if (a.delta && active) {
     const int ncs = (H + 15) >> 4;
     const int nks = (a.Out + 3) >> 2; // uniform
-    with_act(a.act_prev, [&](auto AC) __attribute__((always_inline)) {
+    with_act4(a.act_prev, [&](auto AC) __attribute__((always_inline)) {
       constexpr int A = decltype(AC)::value;
       for (int cb = hr.cb0 + 2 * wave; cb < ncs && cb < hr.cb1; cb += 8) { // wave-uniform; one pass when H <= 128
         const f32x4 wb0 = *reinterpret_cast<const f32x4 *>(s.Wr + (cb * 16 + li) * 16 + g * 4);

@@ -18,12 +18,12 @@ void init_params_host(const std::vector<Layer> &layers, unsigned seed, int mode,
     const size_t w = size_t(L.in) * L.out;
     if (mode == 0) {
       // CPU: normal_distribution<double>(0, scale*sqrt(1/In)) over W and b, fresh per layer.
-      const double sd = (L.act == 2 ? 1.41421356 : 1.0) * std::sqrt(1.0 / double(L.in));
+      const double sd = (act_is_rectifier(L.act) ? 1.41421356 : 1.0) * std::sqrt(1.0 / double(L.in));
       std::normal_distribution<double> dist(0.0, sd);
       for (size_t i = 0; i < w + size_t(L.out); ++i) out[L.off + i] = float(dist(gen));
     } else {
       // CUDA: normal_distribution<float>, weights only, zero biases.
-      const float sd = (L.act == 2 ? 1.41421356f : 1.0f) * std::sqrt(1.0f / float(L.in));
+      const float sd = (act_is_rectifier(L.act) ? 1.41421356f : 1.0f) * std::sqrt(1.0f / float(L.in));
       std::normal_distribution<float> dist(0.0f, sd);
       for (size_t i = 0; i < w; ++i) out[L.off + i] = dist(gen);
       for (int i = 0; i < L.out; ++i) out[L.off + w + i] = 0.0f;

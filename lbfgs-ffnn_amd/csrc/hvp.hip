@@ -14,7 +14,8 @@
 //   R{dZ_L} = s Ysum p .* (R{Z_L} - sum_k p_k R{Z_L}_k)                      (rop_out_xent)
 // The products are the engine's MFMA GEMMs (mlp_curvature.cpp Mlp::hvp); this file holds the elementwise
 // R-steps. act' and act'' are taken through the post-activation value a (act.hpp convention):
-// tanh 1-a^2, -2a(1-a^2); sigmoid a(1-a), a(1-a)(1-2a); relu [a>0], 0; linear 1, 0.
+// tanh 1-a^2, -2a(1-a^2); sigmoid a(1-a), a(1-a)(1-2a); relu [a>0], 0; linear 1, 0; leaky relu [a>0] + 0.01 [a<=0], 0;
+// elu (a<=0: a+1, a+1; else 1, 0); softplus 1-e^-a, e^-a (1-e^-a).
 //
 // Gauss-Newton product G v = J^T H_L J v (Mlp::gnvp): the same R-forward, the convex loss's Hessian
 // H_L applied to R{Z_L}, then an ordinary backward pass. The loss is split from the network at A_L for the
@@ -40,6 +41,8 @@ __device__ __forceinline__ float d2act_rt(int act, float a) {
   switch (act) {
   case ACT_TANH: return -2.0f * a * (1.0f - a * a);
   case ACT_SIGMOID: return a * (1.0f - a) * (1.0f - 2.0f * a);
+  case ACT_ELU: return a > 0.0f ? 0.0f : a + 1.0f;
+  case ACT_SOFTPLUS: return expf(-a) * -expm1f(-a);
   default: return 0.0f;
   }
 }
@@ -210,6 +213,6 @@ void rop_back(hipStream_t s, long long n, const float *T1, const float *T2, cons
   LBF_KERNEL_CHECK();
 }
 
-bool act_has_d2(int act) { return act == ACT_TANH || act == ACT_SIGMOID; }
+bool act_has_d2(int act) { return act == ACT_TANH || act == ACT_SIGMOID || act == ACT_ELU || act == ACT_SOFTPLUS; }
 
 } // namespace lbf

@@ -8,7 +8,23 @@
 
 namespace lbf {
 
-enum Act : int { ACT_LINEAR = 0, ACT_TANH = 1, ACT_RELU = 2, ACT_SIGMOID = 3 };
+enum Act : int {
+  ACT_LINEAR = 0,
+  ACT_TANH = 1,
+  ACT_RELU = 2,
+  ACT_SIGMOID = 3,
+  ACT_LEAKY_RELU = 4, // slope 0.01
+  ACT_ELU = 5,        // alpha 1
+  ACT_SOFTPLUS = 6,
+  ACT_COUNT = 7
+};
+// ReLU and its stand-ins share the sqrt(2) initialisation gain, so swapping one for another keeps a seed's
+// start point bit for bit (host_rng.cpp).
+// The first four: the four-body kernel instances and the fused output-layer kernels carry only these (act.hpp).
+inline bool act_in_heads(int act) { return act >= ACT_LINEAR && act <= ACT_SIGMOID; }
+inline bool act_is_rectifier(int act) {
+  return act == ACT_RELU || act == ACT_LEAKY_RELU || act == ACT_ELU || act == ACT_SOFTPLUS;
+}
 
 // ------------------------------------------------------------------------------------------------
 // GEMM  C[M x N] (row-major, ldc) = op(A)[M x K] * op(B)[K x N]   (fp32 in, fp32 MFMA accumulate)

@@ -24,6 +24,7 @@ int loss_partials_wg(long long B, int Out) {
   return int(w < 1 ? 1 : (w > 1024 ? 1024 : w));
 }
 
+template <bool XACT> // XACT: all seven activation bodies (act.hpp), else the four
 __global__ __launch_bounds__(256) void loss_diff_kernel(const float *A, long long lda, const float *Y, long long ldy,
                                                         const int *idx, long long B, int Out, int act,
                                                         double inv_scale, float *dZ, long long ldz,
@@ -40,7 +41,7 @@ __global__ __launch_bounds__(256) void loss_diff_kernel(const float *A, long lon
     const long long yr = idx ? (long long)idx[b] : b;
     const float d = a - Y[yr * ldy + o];
     acc[0] += double(d) * double(d);
-    dZ[b * ldz + o] = d * dact_rt(act, a) * sc;
+    dZ[b * ldz + o] = d * (XACT ? dact_rt(act, a) : dact_rt4(act, a)) * sc;
   }
   block_sum<1>(acc, scratch);
   if (threadIdx.x == 0) partials[blockIdx.x] = acc[0];
@@ -48,7 +49,7 @@ __global__ __launch_bounds__(256) void loss_diff_kernel(const float *A, long lon
 
 void loss_diff(hipStream_t s, const float *Aout, long long lda, const float *Y, long long ldy, const int *idx,
                long long B, int Out, int act, double inv_scale, float *dZ, long long ldz, double *partials) {
-  hipLaunchKernelGGL(loss_diff_kernel, dim3(loss_partials_wg(B, Out)), dim3(256), 0, s, Aout, lda, Y, ldy, idx, B,
+  hipLaunchKernelGGL(act_in_heads(act) ? loss_diff_kernel<false> : loss_diff_kernel<true>, dim3(loss_partials_wg(B, Out)), dim3(256), 0, s, Aout, lda, Y, ldy, idx, B,
                      Out, act, inv_scale, dZ, ldz, partials);
   LBF_KERNEL_CHECK();
 }

@@ -67,7 +67,7 @@ void Mlp::forward_phase(const float *P, const float *X, const float *Y, const in
   hipStream_t s = ctx_->stream;
   const int nl = int(layers_.size());
   const Layer &Lo = layers_[nl - 1];
-  const bool fused = nl >= 2 && head_supported(Lo.in, Lo.out);
+  const bool fused = head_route();
   ensure(B);
   // the output layer inside the last hidden layer's forward GEMM (EPI_HEAD), when that GEMM is one
   // unsplit tile column: its activations then never reach HBM

@@ -13,7 +13,7 @@ Mlp::Mlp(Ctx *ctx, int nl, const int *dims, const int *acts, const Switches &sw)
   size_t off = 0;
   for (int l = 0; l < nl; ++l) {
     LBF_REQUIRE(dims[l] > 0 && dims[l + 1] > 0, "layer dims must be positive");
-    LBF_REQUIRE(acts[l] >= 0 && acts[l] <= 3, "activation id 0..3");
+    LBF_REQUIRE(acts[l] >= 0 && acts[l] < ACT_COUNT, "activation id 0..6");
     Layer L;
     L.in = dims[l];
     L.out = dims[l + 1];
@@ -72,7 +72,7 @@ void Mlp::plan(long long B) {
   if (planned_ == B) return;
   size_t slab = 0, fslab = 0;
   const int nl = int(layers_.size());
-  const bool fused = nl >= 2 && head_supported(layers_[nl - 1].in, layers_[nl - 1].out);
+  const bool fused = head_route();
   const long long slots = 2LL * ctx_->cus;
   for (auto &L : layers_) {
     // forward GEMM: with fewer row tiles than CUs (a data-parallel rank's shard), split K so the chip
@@ -202,18 +202,25 @@ int Mlp::dx_tile(long long B, int N) const {
   return TILE_AUTO;
 }
 
+bool Mlp::head_route() const {
+  const int nl = int(layers_.size());
+  if (nl < 2) return false;
+  const Layer &Lo = layers_[size_t(nl - 1)], &Lh = layers_[size_t(nl - 2)];
+  return head_supported(Lo.in, Lo.out) && act_in_heads(Lo.act) && act_in_heads(Lh.act);
+}
+
 bool Mlp::rowhead_on(long long B) const {
   const int nl = int(layers_.size());
   if (nl < 2 || B <= 0) return false;
   const Layer &Lo = layers_[size_t(nl - 1)], &Lh = layers_[size_t(nl - 2)];
-  return Lh.fsplits > 1 && rowhead_supported(Lo.in, Lo.out) && head_supported(Lo.in, Lo.out);
+  return Lh.fsplits > 1 && rowhead_supported(Lo.in, Lo.out) && head_route();
 }
 
 bool Mlp::gemm_head_on() const {
   const int nl = int(layers_.size());
   if (nl < 2) return false;
   const Layer &Lo = layers_[size_t(nl - 1)];
-  return head_supported(Lo.in, Lo.out) && layers_[size_t(nl - 2)].fsplits == 1 && Lo.in <= 128;
+  return head_route() && layers_[size_t(nl - 2)].fsplits == 1 && Lo.in <= 128;
 }
 
 void Mlp::ensure(long long B) {
@@ -230,7 +237,7 @@ void Mlp::ensure(long long B) {
   const int nl = int(layers_.size());
   const Layer &Lo = layers_[nl - 1];
   size_t nloss = size_t(loss_partials_wg(std::max(1LL, B), Lo.out));
-  if (nl >= 2 && head_supported(Lo.in, Lo.out)) {
+  if (head_route()) {
     const size_t hw = size_t(std::max({head_nwg(B, Lo.in), gemm_row_tiles(int(std::max(1LL, B)), layers_[nl - 2].ftile),
                                        rowhead_nwg(B)}));
     nloss = std::max(nloss, hw);

@@ -96,6 +96,7 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float *slab, in
   }
 }
 
+template <bool XACT> // XACT: all seven activation bodies (act.hpp), else the four
 __global__ __launch_bounds__(256) void fwd_reduce_act_kernel(const float *slab, int splits, long long stride, int M,
                                                              int N, const float *bias, int act, float *out,
                                                              const int *abort) {
@@ -114,14 +115,14 @@ __global__ __launch_bounds__(256) void fwd_reduce_act_kernel(const float *slab, 
   for (; k < splits; ++k) acc += slab[(long long)k * stride + e];
   const int n = int(e % N);
   const float z = acc + (bias ? bias[n] : 0.0f);
-  out[e] = act_rt(act, z);
+  out[e] = XACT ? act_rt(act, z) : act_rt4(act, z);
 }
 
 void fwd_reduce_act(hipStream_t s, const float *slab, int splits, long long stride, int M, int N, const float *bias,
                     int act, float *out, const int *abort) {
   const long long n = (long long)M * N;
-  hipLaunchKernelGGL(fwd_reduce_act_kernel, dim3(unsigned(cdiv(n, 256))), dim3(256), 0, s, slab, splits, stride, M, N,
-                     bias, act, out, abort);
+  hipLaunchKernelGGL(act_in_heads(act) ? fwd_reduce_act_kernel<false> : fwd_reduce_act_kernel<true>,
+                     dim3(unsigned(cdiv(n, 256))), dim3(256), 0, s, slab, splits, stride, M, N, bias, act, out, abort);
   LBF_KERNEL_CHECK();
 }
 

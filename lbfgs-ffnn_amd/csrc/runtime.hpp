@@ -259,6 +259,7 @@ private:
   void plan(long long B);
   void ensure(long long B);
   bool side_reduced(int l, bool fused) const;
+  bool head_route() const; // the last layer runs in a fused head kernel: its shape and both activations fit one
   bool rowhead_on(long long B) const; // the standalone head fed by the last hidden layer's slabs
   bool gemm_head_on() const; // the output layer runs inside the last hidden layer's forward GEMM
   int dx_tile(long long B, int N) const;

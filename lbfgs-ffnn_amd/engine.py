@@ -14,10 +14,10 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import (ACTS, HVP_MODES, INIT_CPU, INIT_CUDA, LOSSES, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED,
+from ._lib import (HVP_MODES, INIT_CPU, INIT_CUDA, LOSSES, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED,
                    SLBFGS_DP_SLICED, AdamCoef, AdamParams, CgInfo, CgParams, EvalResultC, GdParams, HfParams,
                    HfPrecond, LbfError, LbfgsParams, OwlqnParams, OwlqnStats, Record, SgdParams, SlbfgsParams,
-                   SolveInfo, check, check_l2, check_precond, lib, ptr)
+                   SolveInfo, act_ids, check, check_l2, check_precond, lib, ptr)
 
 
 class Context:
@@ -173,7 +173,7 @@ class Mlp:
         l2 = check_l2(l2)
         self.ctx = ctx
         self.dims = [int(d) for d in dims]
-        self.acts = [ACTS[a] if isinstance(a, str) else int(a) for a in acts]
+        self.acts = act_ids(acts)
         assert len(self.dims) == len(self.acts) + 1
         d = (C.c_int * len(self.dims))(*self.dims)
         a = (C.c_int * len(self.acts))(*self.acts)
@@ -871,7 +871,7 @@ def sgd_solve(net: Mlp, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, 
 
 def init_params_host(dims: Sequence[int], acts: Sequence, seed: int = 123, mode: str = "cpu") -> np.ndarray:
     """Host-side copy of the init stream (for tests; the device path is Mlp.init_params)."""
-    a = [ACTS[x] if isinstance(x, str) else int(x) for x in acts]
+    a = act_ids(acts)
     d = (C.c_int * len(dims))(*[int(x) for x in dims])
     ac = (C.c_int * len(a))(*a)
     n = sum((dims[i] + 1) * dims[i + 1] for i in range(len(a)))

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import engine
-from ._lib import LOSSES, LbfError, check_l2
+from ._lib import LOSSES, LbfError, act_ids, check_l2
 
 
 @dataclass
@@ -157,6 +157,7 @@ class _DeviceNet:
     def addLayer(self, In: int, Out: int, act):
         if self.layers and self.layers[-1][1] != In:
             raise LbfError(f"layer input {In} does not match previous output {self.layers[-1][1]}")
+        act_ids([act])  # an unknown name fails here, not at bindParams
         self.layers.append((int(In), int(Out), act))
 
     def bindParams(self, seed: int = 123, mode: str = "cpu"):
