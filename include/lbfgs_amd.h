@@ -653,6 +653,58 @@ int lbf_prof_read(lbf_ctx *ctx, int cap, int *ids, double *ms, long long *counts
  * batch rows of every timed launch, so a sampled section's flops are 2 * In * Out * work). */
 int lbf_prof_read_work(lbf_ctx *ctx, int cap, int *ids, double *work, int *n_out);
 
+/* ---- Curvature spectrum: device-side Lanczos on the Hessian or the Gauss-Newton matrix (extension; Lanczos 1950,
+ * Golub & Meurant's quadrature). New functions and structs only: LBF_ABI_VERSION stays 3.
+ *
+ * lbf_mlp_lanczos runs prm->steps steps of the Lanczos iteration on A = H(params) + l2 I (matrix LBF_HVP_EXACT,
+ * the product of lbf_mlp_hvp) or A = G(params) + l2 I (LBF_HVP_GAUSS_NEWTON, lbf_mlp_gnvp) on the given batch (same
+ * d_idx / batch / inv_scale meaning, shards summed over a communicator, batch == 0 an empty share), from
+ * q_0 = d_v0 float(1 / |d_v0|). Vectors are fp32; every scalar is an fp64 sum of fixed-order partials formed on the
+ * device (the rules of lbf_mlp_gn_cg: no float atomics, two calls give equal bits). Step j = 0 .. steps - 1:
+ *   w = A q_j                       (Gauss-Newton: one forward pass serves the whole run)
+ *   per pass: c_i = q_i.w for the rows i of R_j, then w -= sum_i float(c_i) q_i
+ *             reorth 1: R_j = {0..j}, two passes;  reorth 0: R_j = {max(0, j-1)..j}, one pass
+ *   alpha_j = the sum over the passes of c_j;   beta_j = |w|
+ *   beta_j <= breakdown_rtol max(|alpha_0..j|, beta_0..j-1): the Krylov space is exhausted, status 1,
+ *             info->steps = j + 1, no q_{j+1};
+ *   alpha_j or beta_j non-finite: status 2, info->steps = j;   else q_{j+1} = w float(1 / beta_j).
+ * Status 0: all steps ran. A zero or non-finite |d_v0| gives status 2 with 0 steps. The host enqueues `check` steps,
+ * then reads the status block; steps enqueued past a stop are no-ops, so the result does not depend on `check`.
+ * h_alpha, h_beta: prm->steps doubles each, zeros from info->steps on; T = tridiag(beta; alpha; beta) of order
+ * info->steps is A restricted to the Krylov space of q_0 (h_beta[info->steps - 1] is the residual norm, not an entry
+ * of T). d_basis (nullable): rows q_0 .. q_steps at stride ld >= parameter count floats; with reorth 1 the run works
+ * in it, with reorth 0 it is written and never read. Without it reorth 1 keeps steps + 1 vectors in a workspace of
+ * the network, reorth 0 three. All device pointers 4-byte aligned; besides the inputs the bits depend only on the
+ * offsets from a 16-byte boundary of d_v0 and of the basis rows a step reads (so with a d_basis on ld % 4: a step
+ * runs on float4 when its rows and the product share one offset, else scalar). With a communicator every rank passes the same d_v0 and
+ * all ranks end with the same bits. LBF_ERR_INVALID: null handles, steps outside 1..128, matrix LBF_HVP_FD or
+ * unknown, reorth outside {0, 1}, check < 1, a negative or non-finite l2 or breakdown_rtol, ld < parameter count
+ * with a basis. Synchronises.
+ *
+ * lbf_tridiag_eig (host only): the eigenvalues of T = tridiag(beta[0..m-2]; alpha[0..m-1]; beta[0..m-2]) by implicit
+ * QL in fp64, ascending into theta[m]; first_sq (nullable, m): the squared first components of the normalised
+ * eigenvectors, the weights of the Gauss quadrature of q_0's spectral measure (they sum to 1); vecs (nullable,
+ * m * m): vecs[i * m + k] is component i of theta[k]'s eigenvector. A zero beta and m == 1 are legal.
+ * LBF_ERR_INVALID: m < 1, a null alpha / theta (beta with m > 1), no convergence (a non-finite entry). */
+typedef struct lbf_lanczos_params {
+  int steps;  /* 32 */
+  int matrix; /* LBF_HVP_GAUSS_NEWTON */
+  int reorth; /* 1 */
+  int check;  /* 8: steps enqueued between two reads of the status block */
+  double l2;  /* 0 */
+  double breakdown_rtol; /* 1.1e-3: the geometric mean of the largest noise-level and the smallest healthy
+                            beta_j / max(|alpha|, beta) measured on the MI355X */
+} lbf_lanczos_params;
+typedef struct lbf_lanczos_info {
+  int steps, status;
+  double v0_norm;
+} lbf_lanczos_info;
+void lbf_lanczos_default_params(lbf_lanczos_params *p);
+int lbf_mlp_lanczos(lbf_mlp *net, const float *d_params, const float *d_v0, const float *d_X, const float *d_Y,
+                    const int *d_idx, long long batch, double inv_scale, const lbf_lanczos_params *prm,
+                    double *h_alpha, double *h_beta, float *d_basis, long long ld, lbf_lanczos_info *info);
+int lbf_tridiag_eig(int m, const double *alpha, const double *beta, double *theta, double *first_sq, double *vecs);
+
 /* ---- device memory, so C/C++ consumers need no HIP headers (the reference's DeviceBuffer,
  * src/cuda/device_buffer.cuh:7-96). kind: 0 host->device, 1 device->host, 2 device->device;
  * lbf_memcpy is ordered on the context stream and returns when the copy is complete. */

@@ -547,6 +547,57 @@ private:
   std::vector<double> trace_;
 };
 
+/// The curvature spectrum of a HipNetwork at its current parameters (HIP extension, no reference counterpart:
+/// lbf_mlp_lanczos and lbf_tridiag_eig): k steps of device-side Lanczos on the Gauss-Newton matrix or the exact Hessian
+/// of the mean loss over `batch` rows, plus l2 I. A class of its own, so that a program using the other classes alone
+/// links against a library that predates these entry points.
+class HipSpectrum {
+public:
+  HipSpectrum(HipHandle &, HipNetwork &net) : net_(net) { lbf_lanczos_default_params(&prm_); }
+  void setSteps(int steps) { prm_.steps = steps; }
+  /// LBF_HVP_GAUSS_NEWTON (default) or LBF_HVP_EXACT
+  void setMatrix(int matrix) { prm_.matrix = matrix; }
+  /// full re-orthogonalisation (default) or the three-vector recurrence
+  void setReorthogonalize(bool on) { prm_.reorth = on ? 1 : 0; }
+  void setL2(double l2) { prm_.l2 = l2; }
+  void setCheck(int check) { prm_.check = check; }
+  void setBreakdownTolerance(double rtol) { prm_.breakdown_rtol = rtol; }
+  /// Runs from the start vector d_v0 (parameter count floats on the device). d_basis (nullable): steps + 1 rows at
+  /// stride ld floats receive the Lanczos vectors. Returns the status: 0 all steps ran, 1 the Krylov space was
+  /// exhausted after steps() steps, 2 a non-finite product or start vector.
+  int lanczos(const HipScalar *d_v0, const HipScalar *input, const HipScalar *target, long long batch,
+              HipScalar *d_basis = nullptr, long long ld = 0) {
+    alpha_.assign(size_t(prm_.steps > 0 ? prm_.steps : 1), 0.0);
+    beta_.assign(alpha_.size(), 0.0);
+    hip_check(lbf_mlp_lanczos(net_.raw(), net_.params_data(), d_v0, input, target, nullptr, batch,
+                              1.0 / double(batch > 0 ? batch : 1), &prm_, alpha_.data(), beta_.data(), d_basis, ld,
+                              &info_),
+              "lbf_mlp_lanczos");
+    return info_.status;
+  }
+  int steps() const { return info_.steps; }
+  int status() const { return info_.status; }
+  const std::vector<double> &alpha() const { return alpha_; } ///< steps() entries count, zeros behind them
+  const std::vector<double> &beta() const { return beta_; }
+  /// The Ritz values of the last run, ascending; weights (nullable): the squared first components of the
+  /// tridiagonal's eigenvectors, the quadrature weights of the start vector's spectral measure.
+  std::vector<double> ritz(std::vector<double> *weights = nullptr) const {
+    std::vector<double> theta(size_t(info_.steps));
+    if (weights) weights->assign(theta.size(), 0.0);
+    if (!theta.empty())
+      hip_check(lbf_tridiag_eig(info_.steps, alpha_.data(), beta_.data(), theta.data(),
+                                weights ? weights->data() : nullptr, nullptr),
+                "lbf_tridiag_eig");
+    return theta;
+  }
+
+private:
+  HipNetwork &net_;
+  lbf_lanczos_params prm_{};
+  lbf_lanczos_info info_{};
+  std::vector<double> alpha_, beta_;
+};
+
 /// Column-major host matrix with the subset of Eigen::MatrixXd's interface the launcher uses.
 class HostMatrix {
 public:

@@ -23,6 +23,7 @@ INIT_CPU, INIT_CUDA = 0, 1
 # LBF_ACT_* of include/lbfgs_amd.h (leaky_relu: slope 0.01, elu: alpha 1; fixed, as torch's defaults)
 ACTS = {"linear": 0, "tanh": 1, "relu": 2, "sigmoid": 3, "leaky_relu": 4, "elu": 5, "softplus": 6}
 LOSSES = {"mse": 0, "softmax_xent": 1}  # LBF_LOSS_MSE, LBF_LOSS_SOFTMAX_XENT
+LANCZOS_MATRICES = {"hessian": 1, "gauss_newton": 2}  # LBF_HVP_EXACT, LBF_HVP_GAUSS_NEWTON (lbf_mlp_lanczos)
 PRECONDS = {"none": 0, "grad_sq": 1}  # LBF_PRECOND_NONE, LBF_PRECOND_GRAD_SQ
 
 
@@ -58,6 +59,15 @@ class CgParams(C.Structure):  # lbf_cg_params
 class CgInfo(C.Structure):  # lbf_cg_info
     _fields_ = [("iterations", C.c_int), ("status", C.c_int), ("rr0", C.c_double), ("rr", C.c_double),
                 ("xb", C.c_double), ("xr", C.c_double), ("xx", C.c_double)]
+
+
+class LanczosParams(C.Structure):  # lbf_lanczos_params
+    _fields_ = [("steps", C.c_int), ("matrix", C.c_int), ("reorth", C.c_int), ("check", C.c_int),
+                ("l2", C.c_double), ("breakdown_rtol", C.c_double)]
+
+
+class LanczosInfo(C.Structure):  # lbf_lanczos_info
+    _fields_ = [("steps", C.c_int), ("status", C.c_int), ("v0_norm", C.c_double)]
 
 
 class HfParams(C.Structure):  # lbf_hf_params
@@ -201,6 +211,10 @@ _SIG = {
     "lbf_hf_precond_default": (None, [C.POINTER(HfPrecond)]),
     "lbf_hf_solve_pc": (C.c_int, [_vp, C.POINTER(HfParams), C.POINTER(HfPrecond), _vp, _vp, _vp, C.c_longlong,
                                   C.c_longlong, C.POINTER(Record), C.POINTER(SolveInfo)]),
+    "lbf_lanczos_default_params": (None, [C.POINTER(LanczosParams)]),
+    "lbf_mlp_lanczos": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.POINTER(LanczosParams),
+                                  _dp, _dp, _vp, C.c_longlong, C.POINTER(LanczosInfo)]),
+    "lbf_tridiag_eig": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "lbf_owlqn_default_params": (None, [C.POINTER(OwlqnParams)]),
     "lbf_owlqn_solve": (C.c_int, [_vp, C.POINTER(OwlqnParams), _vp, _vp, _vp, C.c_longlong, C.c_longlong,
                                   C.POINTER(Record), C.POINTER(SolveInfo), C.POINTER(OwlqnStats)]),

@@ -5,6 +5,7 @@
 #include "host_rng.hpp"
 #include "runtime.hpp"
 #include "solvers.hpp"
+#include "tridiag.hpp"
 
 #include <rccl/rccl.h>
 
@@ -585,6 +586,47 @@ int lbf_mlp_gn_cg_residual(lbf_mlp *net, float *d_r) {
     LBF_HIP(hipMemcpyAsync(d_r, net->net->cg_residual(), net->net->nparams() * sizeof(float), hipMemcpyDeviceToDevice,
                            s));
     LBF_HIP(hipStreamSynchronize(s));
+  });
+}
+
+void lbf_lanczos_default_params(lbf_lanczos_params *p) {
+  if (!p) return;
+  p->steps = 32;
+  p->matrix = LBF_HVP_GAUSS_NEWTON;
+  p->reorth = 1;
+  p->check = 8;
+  p->l2 = 0.0;
+  p->breakdown_rtol = 1.1e-3;
+}
+
+int lbf_mlp_lanczos(lbf_mlp *net, const float *d_params, const float *d_v0, const float *d_X, const float *d_Y,
+                    const int *d_idx, long long batch, double inv_scale, const lbf_lanczos_params *prm,
+                    double *h_alpha, double *h_beta, float *d_basis, long long ld, lbf_lanczos_info *info) {
+  return guard([&] {
+    // the parameters first, so that a caller without a device still learns which of them is wrong
+    LBF_REQUIRE(prm, "null parameters");
+    LBF_REQUIRE(prm->steps >= 1 && prm->steps <= LZ_MAX_STEPS, "steps must be in 1..128");
+    LBF_REQUIRE(prm->matrix == LBF_HVP_EXACT || prm->matrix == LBF_HVP_GAUSS_NEWTON,
+                "matrix must be LBF_HVP_EXACT or LBF_HVP_GAUSS_NEWTON");
+    LBF_REQUIRE(prm->reorth == 0 || prm->reorth == 1, "reorth must be 0 or 1");
+    LBF_REQUIRE(prm->check >= 1, "check must be >= 1");
+    LBF_REQUIRE(std::isfinite(prm->l2) && prm->l2 >= 0.0, "l2 must be finite and >= 0");
+    LBF_REQUIRE(std::isfinite(prm->breakdown_rtol) && prm->breakdown_rtol >= 0.0,
+                "breakdown_rtol must be finite and >= 0");
+    LBF_REQUIRE(net && d_params && d_v0 && h_alpha && h_beta && batch >= 0 && (batch == 0 || (d_X && d_Y)),
+                "null handle or bad batch");
+    net->ctx->c.set_device();
+    Mlp::LanczosInfo li;
+    net->net->lanczos(d_params, d_v0, d_X, d_Y, d_idx, batch, inv_scale, prm->l2, prm->matrix == LBF_HVP_EXACT,
+                      prm->steps, prm->reorth != 0, prm->check, prm->breakdown_rtol, h_alpha, h_beta, d_basis, ld, &li);
+    if (info) *info = lbf_lanczos_info{li.steps, li.status, li.v0_norm};
+  });
+}
+
+int lbf_tridiag_eig(int m, const double *alpha, const double *beta, double *theta, double *first_sq, double *vecs) {
+  return guard([&] {
+    LBF_REQUIRE(m >= 1 && alpha && theta && (m == 1 || beta), "m >= 1, alpha, theta and (m > 1) beta");
+    LBF_REQUIRE(tridiag_eig(m, alpha, beta, theta, first_sq, vecs), "the QL iteration did not converge");
   });
 }
 

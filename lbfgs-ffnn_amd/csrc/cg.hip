@@ -11,7 +11,7 @@
 // mixed offsets (a caller's x or b one float off, the solver's own r, p, Ap aligned) the whole sweep is scalar.
 #include "internal.hpp"
 #include "kernels.hpp"
-#include "wave.hpp"
+#include "sweep.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -21,46 +21,6 @@ namespace lbf {
 namespace {
 
 constexpr int kCgMaxWg = 1024; // the cap of loss_partials_wg: 4 workgroups on each of 256 CUs, 1024-word tables
-
-// Elements [0, head) and [tail0, n) one at a time, [head, tail0) as nvec float4 groups.
-struct Span {
-  long long n, head, nvec, tail0;
-};
-
-template <class... P> Span make_span(long long n, P... ptrs) {
-  const int lead = common_lead(ptrs...);
-  Span sp{n, n, 0, n};
-  if (lead >= 0) {
-    sp.head = std::min<long long>(n, lead);
-    sp.nvec = (n - sp.head) / 4;
-    sp.tail0 = sp.head + 4 * sp.nvec;
-  }
-  return sp;
-}
-
-// The scalar elements of a span as one index range: j < head is element j, then tail0 + (j - head).
-__device__ __forceinline__ long long span_nscalar(const Span &sp) { return sp.head + (sp.n - sp.tail0); }
-__device__ __forceinline__ long long span_elem(const Span &sp, long long j) {
-  return j < sp.head ? j : sp.tail0 + (j - sp.head);
-}
-
-// The sum of a partial table, the same bits in every workgroup that calls it.
-__device__ __forceinline__ double table_sum(const double *t, int nwg, double *wv) {
-  double q = 0.0;
-  for (int i = threadIdx.x; i < nwg; i += 256) q += t[i];
-  return block_sum_all(q, wv);
-}
-
-// The abort word read once per workgroup, so that all its waves take the same branch even when workgroup 0 of
-// this very launch raises the word meanwhile.
-__device__ __forceinline__ bool block_aborted(const int *abort) {
-  __shared__ int flag;
-  if (threadIdx.x == 0) flag = abort_flag(abort);
-  __syncthreads();
-  return flag != 0;
-}
-
-__device__ __forceinline__ bool finite_pos(double v) { return v > 0.0 && v <= 1.7976931348623157e308; }
 
 // PC (all three sweeps): preconditioned CG with the diagonal inverse preconditioner minv. z = minv .* r is formed
 // in registers wherever it is needed and never stored; rz holds the partials of r.z like rr those of r.r. With

@@ -350,6 +350,45 @@ void cg_dir(hipStream_t s, const CgArgs &a, int k);
 void cg_xdots(hipStream_t s, const CgArgs &a);
 
 // ------------------------------------------------------------------------------------------------
+// Device-side Lanczos on a symmetric A (lanczos.hip; the driver and A = H + l2 I or G + l2 I are Mlp::lanczos;
+// DESIGN §23). Step j: the product w = A q_j, then per pass lz_orth (the dots c_i = q_i.w over the rows of the
+// launch, w -= sum_i float(c_i) q_i), then lz_finish: alpha_j = the sum over the passes of c_j, beta_j = |w|,
+//   beta_j <= breakdown_rtol max(|alpha_0..j|, beta_0..j-1): LZ_EXHAUSTED, steps = j + 1, no q_{j+1};
+//   alpha_j or beta_j non-finite: LZ_FAILED, steps = j;   else q_{j+1} = w float(1 / beta_j).
+// Scalars, tables, grid (cg_nwg(n) workgroups whatever j is) and the abort word follow the rules of the CG sweeps
+// above: a stopped run turns what was enqueued behind it into no-ops. Vectors 4-byte aligned; a launch runs on
+// float4 when all its vectors, the rows included, share their offset from a 16-byte boundary.
+// ------------------------------------------------------------------------------------------------
+constexpr int LZ_MAX_STEPS = 128;
+enum { LZ_STEPS = 0, LZ_STATUS = 1, LZ_V0NORM = 2, LZ_ALPHA = 8, LZ_BETA = LZ_ALPHA + LZ_MAX_STEPS,
+       LZ_SCALE = LZ_BETA + LZ_MAX_STEPS, LZ_N = LZ_SCALE + LZ_MAX_STEPS };
+enum { LZ_RUNNING = -1, LZ_DONE = 0, LZ_EXHAUSTED = 1, LZ_FAILED = 2 };
+// The basis rows of one launch: row i < nrows is slot slot0 + i of Q (stride ld floats), wrapped once at `ring`
+// slots when ring > 0 (the three-vector recurrence), so nrows <= ring then.
+struct LzRows {
+  const float *Q = nullptr;
+  long long ld = 0;
+  int slot0 = 0, nrows = 0, ring = 0;
+};
+struct LzArgs {
+  long long n = 0;
+  float *w = nullptr;       // the product, orthogonalised in place
+  double *tab = nullptr;    // [2 passes][lz_pass_words(n)] partials of the dots, [row][cg_nwg(n)]
+  double *wwtab = nullptr;  // [cg_nwg(n)] partials of w.w (lz_start: of v0.v0)
+  double *st = nullptr;     // LZ_N status words, zero before lz_start
+  int *abort = nullptr;     // the run's abort word
+  int steps = 0;
+  double breakdown_rtol = 0.0;
+};
+size_t lz_pass_words(long long n);
+// q0 (and q0b, nullable) = v0 float(1 / |v0|); a zero or non-finite |v0|: LZ_FAILED, 0 steps
+void lz_start(hipStream_t s, const LzArgs &a, const float *v0, float *q0, float *q0b);
+// one orthogonalisation pass of a.w against R; last: also the partials of the new w.w
+void lz_orth(hipStream_t s, const LzArgs &a, const LzRows &R, int pass, bool last);
+// col: q_j's row in the passes' tables; qn (and qnb, nullable): where q_{j+1} goes
+void lz_finish(hipStream_t s, const LzArgs &a, int j, int npass, int col, float *qn, float *qnb);
+
+// ------------------------------------------------------------------------------------------------
 // Orthant-wise sweeps of OWL-QN (owlqn.hip; the solver is run_owlqn) on F = f + sum_i c_i |x_i|,
 // c_i = float(l1) on the penalised coordinates and 0 on the free ones. Both launch ww_partials_n(n) workgroups over
 // the element blocks of WwPart, write one fp64 partial per workgroup and table, and are followed by a

@@ -6,6 +6,14 @@
 
 namespace lbf {
 
+namespace {
+struct AbortScope { // ctx->abort points at a solver's own word for the duration of its run (gn_cg, lanczos)
+  Ctx *c;
+  const int *prev;
+  ~AbortScope() { c->abort = prev; }
+};
+} // namespace
+
 // The products of the R-pass (hvp, gnvp): the engine's GEMM plans on the R-pass workspace.
 void Mlp::rpass_ensure(long long B) {
   if (B <= rcap_) return;
@@ -257,11 +265,7 @@ void Mlp::gn_cg(const float *P, const float *b, float bscale, const float *X, co
   a.abort = cg_abort_.get();
   a.max_iters = max_iters;
   a.tol2 = rtol * rtol;
-  struct AbortScope { // ctx->abort points at the solver's word for the duration of the solve
-    Ctx *c;
-    const int *prev;
-    ~AbortScope() { c->abort = prev; }
-  } scope{ctx_, ctx_->abort};
+  AbortScope scope{ctx_, ctx_->abort};
   LBF_HIP(hipMemsetAsync(cg_abort_.get(), 0, sizeof(int), s));
   ctx_->abort = cg_abort_.get();
   gn_prepare(P, X, idx, B);
@@ -296,6 +300,94 @@ void Mlp::gn_cg(const float *P, const float *b, float bscale, const float *X, co
     info->xb = hst[CG_XB];
     info->xr = hst[CG_XR];
     info->xx = hst[CG_XX];
+  }
+}
+
+// Lanczos on H + l2 I or G + l2 I (lanczos.hip), enqueued ahead like gn_cg: every launch of a step takes
+// the run's abort word, so the steps enqueued past a stop change nothing and the result does not depend on `check`.
+// Under a communicator a frozen step still joins its all-reduce, so w is zeroed in front of every product there.
+// gn_apply is frozen as a whole and the collective sums zeros. Of hvp the GEMMs and the slab sums are frozen (they
+// take ctx->abort), its elementwise launches are not: its `dst += seg_` adds one stale segment to the zeros, so the
+// collective sums at most that, the same on every step, and w cannot grow from one frozen step to the next. No
+// launch of the run reads w after the stop.
+void Mlp::lanczos(const float *P, const float *v0, const float *X, const float *Y, const int *idx, long long B,
+                  double inv_scale, double l2, bool exact, int steps, bool reorth, int check, double breakdown_rtol,
+                  double *h_alpha, double *h_beta, float *basis, long long ld, LanczosInfo *info) {
+  const long long n = (long long)nparams_;
+  LBF_REQUIRE(P && v0 && h_alpha && h_beta && B >= 0 && (B == 0 || (X && Y)), "lanczos: bad argument");
+  LBF_REQUIRE(steps >= 1 && steps <= LZ_MAX_STEPS && check >= 1, "lanczos: steps in 1..128, check >= 1");
+  LBF_REQUIRE(std::isfinite(l2) && l2 >= 0.0 && std::isfinite(breakdown_rtol) && breakdown_rtol >= 0.0,
+              "lanczos: l2 and breakdown_rtol must be finite and >= 0");
+  LBF_REQUIRE(!basis || ld >= n, "lanczos: ld < parameter count");
+  hipStream_t s = ctx_->stream;
+  const int nwg = cg_nwg(n);
+  // the rows the run reads: the caller's basis, or a workspace of steps + 1 rows (reorth) or a ring of three
+  const int ring = reorth ? 0 : 3;
+  float *Q = basis;
+  long long qld = ld;
+  if (!reorth || !basis) {
+    qld = round4(n);
+    lz_q_.ensure(size_t(reorth ? steps + 1 : 3) * size_t(qld));
+    Q = lz_q_.get();
+  }
+  float *out = reorth ? nullptr : basis; // reorth = 0 with a basis: every q_j is also copied out
+  auto row = [&](int j) { return Q + size_t(ring ? j % ring : j) * size_t(qld); };
+  auto out_row = [&](int j) { return out ? out + size_t(j) * size_t(ld) : nullptr; };
+  lz_w_.ensure(size_t(n));
+  lz_part_.ensure(2 * lz_pass_words(n) + size_t(nwg));
+  lz_st_.ensure(LZ_N);
+  lz_abort_.ensure(1);
+  lz_hst_.ensure(LZ_N);
+  LzArgs a;
+  a.n = n;
+  a.w = lz_w_.get();
+  a.tab = lz_part_.get();
+  a.wwtab = lz_part_.get() + 2 * lz_pass_words(n);
+  a.st = lz_st_.get();
+  a.abort = lz_abort_.get();
+  a.steps = steps;
+  a.breakdown_rtol = breakdown_rtol;
+  AbortScope scope{ctx_, ctx_->abort};
+  LBF_HIP(hipMemsetAsync(lz_abort_.get(), 0, sizeof(int), s));
+  LBF_HIP(hipMemsetAsync(lz_st_.get(), 0, LZ_N * sizeof(double), s));
+  ctx_->abort = lz_abort_.get();
+  if (!exact) gn_prepare(P, X, idx, B);
+  lz_start(s, a, v0, row(0), out_row(0));
+  double *hst = lz_hst_.get();
+  const int npass = reorth ? 2 : 1;
+  int j = 0;
+  for (;;) {
+    const int m = std::min(check, steps - j);
+    for (int i = 0; i < m; ++i, ++j) {
+      if (ctx_->dp() && B > 0) zero_fill(s, n, a.w);
+      if (exact) {
+        hvp(P, row(j), X, Y, idx, B, inv_scale, l2, a.w);
+      } else {
+        gn_apply(P, row(j), X, Y, idx, B, inv_scale, l2, a.w);
+      }
+      LzRows R;
+      R.Q = Q;
+      R.ld = qld;
+      R.ring = ring;
+      const int r0 = reorth ? 0 : std::max(0, j - 1);
+      R.slot0 = ring ? r0 % ring : r0;
+      R.nrows = j - r0 + 1;
+      for (int p = 0; p < npass; ++p) lz_orth(s, a, R, p, p + 1 == npass);
+      lz_finish(s, a, j, npass, j - r0, row(j + 1), out_row(j + 1));
+    }
+    LBF_HIP(hipMemcpyAsync(hst, lz_st_.get(), LZ_N * sizeof(double), hipMemcpyDeviceToHost, s));
+    LBF_HIP(hipStreamSynchronize(s));
+    if (int(hst[LZ_STATUS]) != LZ_RUNNING || j >= steps) break;
+  }
+  const int done = int(hst[LZ_STEPS]);
+  for (int i = 0; i < steps; ++i) {
+    h_alpha[i] = i < done ? hst[LZ_ALPHA + i] : 0.0;
+    h_beta[i] = i < done ? hst[LZ_BETA + i] : 0.0;
+  }
+  if (info) {
+    info->steps = done;
+    info->status = int(hst[LZ_STATUS]);
+    info->v0_norm = hst[LZ_V0NORM];
   }
 }
 

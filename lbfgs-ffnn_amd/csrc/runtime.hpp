@@ -210,6 +210,19 @@ public:
   // like forward(). Bitwise reproducible.
   void grad_sq(const float *P, const float *X, const float *Y, const int *idx, long long B, double scale, float *out);
   const float *cg_residual() const { return cg_r_.get(); } // r of the last gn_cg (null before the first)
+  // `steps` steps of Lanczos on A = H(P) + l2 I (exact) or G(P) + l2 I from q_0 = v0 / |v0| (lanczos.hip; DESIGN
+  // §23): the tridiagonal's alpha and beta into h_alpha / h_beta (steps doubles each, zeros from info->steps on).
+  // G: one gn_prepare, then gn_apply per step; H: hvp per step. reorth: every step orthogonalises twice against
+  // all earlier rows (steps + 1 rows are kept: in basis when given, else in a workspace); otherwise once against
+  // q_{j-1} and q_j, three rows in a ring, and basis is only written. The host enqueues `check` steps per status
+  // read; what is enqueued behind a stop is frozen by the run's abort word. Synchronous.
+  struct LanczosInfo {
+    int steps = 0, status = 0; // LZ_DONE / LZ_EXHAUSTED / LZ_FAILED
+    double v0_norm = 0.0;
+  };
+  void lanczos(const float *P, const float *v0, const float *X, const float *Y, const int *idx, long long B,
+               double inv_scale, double l2, bool exact, int steps, bool reorth, int check, double breakdown_rtol,
+               double *h_alpha, double *h_beta, float *basis, long long ld, LanczosInfo *info);
   // Device-side evaluation (metrics.hip; replaces the host scan of unified_launcher.hpp:154-199): forward() and
   // the metrics kernel per chunk of chunk_rows rows (0: 65536, or the batch if smaller), so the activation
   // workspace is bounded by the chunk. Every chunk runs the forward plan of the whole batch, so the outputs, and
@@ -344,6 +357,13 @@ private:
   DevBuf<double> cg_part_, cg_st_;
   DevBuf<int> cg_abort_;
   PinnedBuf<double> cg_hst_;
+  // ---- Lanczos state (lanczos) ----
+  // the basis rows (a ring of three, or steps + 1 without a caller's basis), w, the tables [dots x 2 passes | w.w],
+  // the status block, the abort word
+  DevBuf<float> lz_q_, lz_w_;
+  DevBuf<double> lz_part_, lz_st_;
+  DevBuf<int> lz_abort_;
+  PinnedBuf<double> lz_hst_;
   // ---- evaluate buffers ----
   // per-workgroup loss partials and counts [rows, correct, topk] of every chunk, the confusion cells,
   // the partials' sum, the all-reduce words

@@ -14,10 +14,17 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import (HVP_MODES, INIT_CPU, INIT_CUDA, LOSSES, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED,
+from ._lib import (HVP_MODES, INIT_CPU, INIT_CUDA, LANCZOS_MATRICES, LOSSES, LS_ARMIJO, LS_WOLFE, SLBFGS_DP_REPLICATED,
                    SLBFGS_DP_SLICED, AdamCoef, AdamParams, CgInfo, CgParams, EvalResultC, GdParams, HfParams,
-                   HfPrecond, LbfError, LbfgsParams, OwlqnParams, OwlqnStats, Record, SgdParams, SlbfgsParams,
-                   SolveInfo, act_ids, check, check_l2, check_precond, lib, ptr)
+                   HfPrecond, LanczosInfo, LanczosParams, LbfError, LbfgsParams, OwlqnParams, OwlqnStats, Record,
+                   SgdParams, SlbfgsParams, SolveInfo, act_ids, check, check_l2, check_precond, lib, ptr)
+
+_check = check  # for the methods that have an argument of their own named `check`
+
+
+def _dptr(a: np.ndarray):
+    """A float64 host array as the double * of a C call."""
+    return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 class Context:
@@ -435,6 +442,46 @@ class Mlp:
         """finite_difference_hvp_batch (s_lbfgs.hpp:88-101), the S-LBFGS curvature pair's y."""
         return self._product("lbf_mlp_fd_hvp", params, v, X, Y, idx, inv_scale, l2, out, eps)
 
+    def lanczos(self, params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, steps: int = 32,
+                matrix: str = "gauss_newton", l2: float = 0.0, idx: Optional[torch.Tensor] = None,
+                inv_scale: Optional[float] = None, v0: Optional[torch.Tensor] = None, seed: int = 0,
+                reorth: bool = True, basis=False, check: int = 8,
+                breakdown_rtol: Optional[float] = None) -> "LanczosResult":
+        """`steps` steps of device-side Lanczos (lbf_mlp_lanczos) on the Gauss-Newton matrix ("gauss_newton") or the
+        exact Hessian ("hessian") of the loss_grad batch loss at params, plus l2 I. v0 None: the start vector is
+        torch.randn from a CPU generator seeded with `seed`, so it is reproducible and the same on every rank.
+        reorth: full re-orthogonalisation (steps + 1 vectors kept) or the three-vector recurrence. basis: True
+        returns the Lanczos vectors; a float32 device tensor [>= steps + 1][ld >= nparams] receives them in place.
+        The Ritz values (ascending) and quadrature weights come from lbf_tridiag_eig on the host."""
+        if matrix not in LANCZOS_MATRICES:
+            raise LbfError(f"unknown matrix {matrix!r}: expected one of {sorted(LANCZOS_MATRICES)}")
+        B, inv_scale, _ = self._batch(X, Y, idx, inv_scale)
+        n, steps = self.nparams, int(steps)
+        p = LanczosParams()
+        lib().lbf_lanczos_default_params(C.byref(p))
+        p.steps, p.matrix, p.reorth, p.check, p.l2 = steps, LANCZOS_MATRICES[matrix], int(bool(reorth)), int(check), l2
+        if breakdown_rtol is not None:
+            p.breakdown_rtol = breakdown_rtol
+        if v0 is None:
+            v0 = torch.randn(n, generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float32).to(params.device)
+        Q, ld = None, 0
+        if torch.is_tensor(basis):
+            if basis.dim() != 2 or basis.shape[0] < steps + 1 or basis.shape[1] < n:
+                raise LbfError(f"basis must be [>= {steps + 1}][>= {n}], got {tuple(basis.shape)}")
+            Q, ld = basis, int(basis.shape[1])
+        elif basis:
+            ld = (n + 3) // 4 * 4  # the row stride of the network's own workspace: the same float4 routes, the same bits
+            Q = torch.empty((max(steps, 0) + 1, ld), dtype=torch.float32, device=params.device)
+        alpha, beta = np.zeros(max(steps, 1)), np.zeros(max(steps, 1))
+        info = LanczosInfo()
+        _check(lib().lbf_mlp_lanczos(self.h, ptr(params, numel=n), ptr(v0, numel=n), ptr(X), ptr(Y),
+                                     ptr(idx, torch.int32), B, inv_scale, C.byref(p), _dptr(alpha), _dptr(beta),
+                                     ptr(Q), ld, C.byref(info)), "lbf_mlp_lanczos")
+        m = int(info.steps)
+        rows = m + 1 if info.status == 0 else m  # an exhausted or failed run has no q_m
+        return LanczosResult(alpha=alpha[:steps], beta=beta[:steps], steps=m, status=int(info.status),
+                             v0_norm=float(info.v0_norm), basis=None if Q is None else Q[:rows, :n])
+
     def __del__(self):
         try:
             if getattr(self, "h", None):
@@ -442,6 +489,92 @@ class Mlp:
                 self.h = None
         except Exception:
             pass
+
+
+def tridiag_eig(alpha, beta, vectors: bool = False):
+    """Eigenvalues (ascending) of the symmetric tridiagonal matrix with diagonal alpha[0..m-1] and off-diagonal
+    beta[0..m-2] (lbf_tridiag_eig: implicit QL in fp64 on the host; entries of beta past m - 1 are ignored), and the
+    squared first components of its eigenvectors. Returns (theta, weights), and with vectors also the m x m matrix
+    whose column k is theta[k]'s eigenvector."""
+    a = np.ascontiguousarray(alpha, np.float64)
+    m = int(a.size)
+    b = np.ascontiguousarray(np.asarray(beta, np.float64)[:max(m - 1, 0)])
+    if m < 1 or b.size < m - 1:
+        raise LbfError(f"tridiag_eig: {m} diagonal entries need {max(m - 1, 0)} off-diagonal ones, got {b.size}")
+    b = np.concatenate([b, np.zeros(1)])  # never a null pointer, also for m == 1
+    theta, w = np.zeros(m), np.zeros(m)
+    vecs = np.zeros((m, m)) if vectors else None
+    check(lib().lbf_tridiag_eig(m, _dptr(a), _dptr(b), _dptr(theta), _dptr(w), _dptr(vecs) if vectors else None),
+          "lbf_tridiag_eig")
+    return (theta, w, vecs) if vectors else (theta, w)
+
+
+@dataclass
+class LanczosResult:
+    """What Mlp.lanczos returns. alpha, beta: the recurrence's coefficients (length = the steps asked for, zeros from
+    `steps` on); T = tridiag(beta[:steps-1]; alpha[:steps]). status 0: every step ran; 1: the Krylov space of the
+    start vector was exhausted after `steps` steps (the Ritz values are then eigenvalues); 2: a non-finite product
+    or start vector. ritz (ascending) and weights (the squared first components of T's eigenvectors: the Gauss
+    quadrature of the start vector's spectral measure, summing to 1) are empty when steps == 0."""
+    alpha: np.ndarray
+    beta: np.ndarray
+    steps: int
+    status: int
+    v0_norm: float
+    basis: Optional[torch.Tensor] = None  # rows q_0 .. (q_steps when status == 0), when asked for
+    ritz: Optional[np.ndarray] = None
+    weights: Optional[np.ndarray] = None
+
+    def __post_init__(self):
+        if self.steps > 0:
+            self.ritz, self.weights = tridiag_eig(self.alpha[:self.steps], self.beta[:self.steps])
+        else:
+            self.ritz, self.weights = np.zeros(0), np.zeros(0)
+
+    def ritz_vectors(self, which=None) -> torch.Tensor:
+        """The Ritz vectors Q s_k of ritz[which] (an index, a list of them, None: all) as rows of a float32 device
+        tensor; needs the basis."""
+        if self.basis is None:
+            raise LbfError("ritz_vectors needs the Lanczos vectors: call lanczos(..., basis=True)")
+        if self.steps == 0:
+            raise LbfError("ritz_vectors: the run took no step")
+        _, _, S = tridiag_eig(self.alpha[:self.steps], self.beta[:self.steps], vectors=True)
+        sel = np.arange(self.steps) if which is None else np.atleast_1d(np.asarray(which, np.int64))
+        coef = torch.from_numpy(np.ascontiguousarray(S[:, sel].T, np.float32)).to(self.basis.device)
+        return coef @ self.basis[:self.steps]
+
+
+def slq_density(ritz_list, weight_list, grid, sigma: float) -> np.ndarray:
+    """Stochastic Lanczos quadrature: the eigenvalue density on `grid`, each probe's Ritz values broadened by a
+    Gaussian of width sigma and weighted by its quadrature weights, averaged over the probes. Pure host arithmetic;
+    integrates to 1 on a grid that covers the spectrum."""
+    grid = np.asarray(grid, np.float64)
+    if len(ritz_list) == 0 or len(ritz_list) != len(weight_list) or not sigma > 0.0:
+        raise LbfError("slq_density: one weight list per Ritz list, at least one probe, sigma > 0")
+    dens = np.zeros_like(grid)
+    for theta, w in zip(ritz_list, weight_list):
+        theta, w = np.asarray(theta, np.float64), np.asarray(w, np.float64)
+        z = (grid[:, None] - theta[None, :]) / sigma
+        dens += (np.exp(-0.5 * z * z) * w[None, :]).sum(1) / (sigma * np.sqrt(2.0 * np.pi))
+    return dens / len(ritz_list)
+
+
+def spectral_density(net: "Mlp", params: torch.Tensor, X: torch.Tensor, Y: torch.Tensor, probes: int = 4,
+                     steps: int = 32, grid=None, sigma: Optional[float] = None, seed: int = 0, **kw):
+    """The eigenvalue density of the curvature matrix by stochastic Lanczos quadrature: `probes` runs of Mlp.lanczos
+    from the start vectors of seeds seed, seed + 1, .. (kw goes to lanczos: matrix, l2, idx, inv_scale, reorth,
+    check), then slq_density. grid None: 512 points over the Ritz values' range widened by 5 sigma; sigma None: 1 %
+    of that range. Returns (grid, density, results)."""
+    runs = [net.lanczos(params, X, Y, steps=steps, seed=seed + p, **kw) for p in range(int(probes))]
+    runs = [r for r in runs if r.steps > 0]
+    if not runs:
+        raise LbfError("spectral_density: no probe took a step")
+    lo, hi = min(r.ritz[0] for r in runs), max(r.ritz[-1] for r in runs)
+    if sigma is None:
+        sigma = 0.01 * max(hi - lo, abs(hi), 1e-30)
+    if grid is None:
+        grid = np.linspace(lo - 5.0 * sigma, hi + 5.0 * sigma, 512)
+    return np.asarray(grid, np.float64), slq_density([r.ritz for r in runs], [r.weights for r in runs], grid, sigma), runs
 
 
 class History:

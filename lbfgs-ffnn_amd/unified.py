@@ -551,5 +551,24 @@ class UnifiedLauncher:
         x, y = (d.x, d.y) if split == "train" else (d.test_xs, d.test_ys)
         return self.eval_mlp_.evaluate(nw.params, x, y, k=k, confusion=confusion)
 
+    def spectrum(self, split: str = "train", steps: int = 32, matrix: str = "gauss_newton", **kw):
+        """The curvature spectrum at the current parameters (engine.Mlp.lanczos, an engine.LanczosResult): `steps`
+        steps of Lanczos on the Gauss-Newton matrix or the exact Hessian ("hessian") of the mean loss over a split,
+        plus the network's l2. Under data parallelism each rank passes its shard and every rank gets the same bits.
+        kw: seed, v0, reorth, basis, check. Like metrics() it runs on a network of its own."""
+        if split not in ("train", "test"):
+            raise LbfError(f"split must be 'train' or 'test', got {split!r}")
+        d = self.data_
+        if d is None or (split == "test" and d.test_xs is None):
+            raise LbfError(f"no {split} split: call setData() with one first")
+        nw = self.net_wrapper_
+        if getattr(self, "spec_mlp_", None) is None:
+            self.spec_mlp_ = engine.Mlp(self.ctx, nw.mlp.dims, nw.mlp.acts, loss=nw.loss)
+        elif self.spec_mlp_.loss_name != nw.loss:
+            self.spec_mlp_.loss_name = nw.loss
+        x, y, rows = (d.x, d.y, d.n_global) if split == "train" else (d.test_xs, d.test_ys, d.n_test)
+        return self.spec_mlp_.lanczos(nw.params, x, y, steps=steps, matrix=matrix, l2=nw.mlp.l2,
+                                      inv_scale=1.0 / max(rows, 1), **kw)
+
     def getWrapper(self):
         return self.net_wrapper_
